@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: samples/s of PreWorld's camera->voxel occupancy hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C2] [--mode replicas|sharded] [--no-graph]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C2] [--mode replicas|sharded] [--no-graph] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -31,6 +31,10 @@ The JSON line also carries
                   (median of 5 after a warm-up) and the OpenMP port (the reference has no CPU path for its native ops).
   extra        -- measured after the timed region: c2 (single frame, 1 state), c5 (render head forward / forward + backward, the
                   pre-train step), train (the voxel-side fine-tune step, forward + backward); --no-extra skips them.
+
+--dump-outputs DIR writes the result of the last timed step (rank 0's) as DIR/<name>.npy (float32; arrays above 2^20 elements as a
+seeded sample of 2^19; at most 64 MB in all) and lists them under `dump_outputs`: the same arguments give the same inputs on every
+run, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -66,6 +70,44 @@ def make_inputs(dev, seed, n_frames):
     frames = harness.lifted_frames(seed, 6, dev, n_frames=n_frames)
     ego = torch.from_numpy(S.ego_state(seed)).to(dev)
     return frames, ego
+
+
+# ------------------------------------------------------------------------------ --dump-outputs
+DUMP_MAX_BYTES = 64 * 10 ** 6      # one dump, all files together
+DUMP_WHOLE_MAX = 1 << 20           # arrays of up to this many elements are written whole,
+DUMP_SAMPLE = 1 << 19              # larger ones as this many elements at fixed positions (seed 0, sorted, drawn from the flat index)
+
+
+def dump_outputs(out, path):
+    """Writes the result dict of the last timed step to path/<name>.npy, float32 (float64 stays float64): every tensor a caller
+    receives, one file each (a list entry of more than one tensor becomes <name>_<i>), h2 storage expanded exactly to fp32.
+    'grids' is skipped: it holds the same bytes as the semantic_occ_* / geo_occ_* entries.  Inputs and sample positions depend
+    only on the command line, so two builds can be compared file by file.  Returns {name: shape written}."""
+    def host(t):
+        if isinstance(t, ops.H2):
+            t = ops.h2_to_f32(t)
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        if t.numel() > DUMP_WHOLE_MAX:
+            idx = np.sort(np.random.RandomState(0).randint(0, t.numel(), DUMP_SAMPLE))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        return t.cpu().numpy()
+    arrays = {}
+    for key, v in out.items():
+        if key == 'grids' or v is None:
+            continue
+        if isinstance(v, (list, tuple)):
+            for i, t in enumerate(v):
+                arrays[key if len(v) == 1 else '%s_%d' % (key, i)] = host(t)
+        else:
+            arrays[key] = host(v)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit('bench.py --dump-outputs: %d bytes, more than %d' % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+    return {name: list(a.shape) for name, a in sorted(arrays.items())}
 
 
 # ------------------------------------------------------------------------------ roofline probe
@@ -381,7 +423,8 @@ def c5_result(args, quick=False):
     consts = head.consts(torch.eye(3))
     b = torch.linspace(0, 2, 97)
     t96 = ((b[1:] + b[:-1]) * 0.5).to(dev).contiguous()
-    steps = 20 if quick else max(args.steps, 20)
+    steps = 20 if quick else args.steps
+    last = {}                                   # what the headline's last timed step (mixed scene, forward + backward) computed
 
     def timed(fn, steps, warmup):
         for _ in range(warmup):
@@ -389,9 +432,9 @@ def c5_result(args, quick=False):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
-            fn()
+            out = fn()
         torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / steps
+        return (time.perf_counter() - t0) / steps, out
 
     def scene(name):
         if name == 'mixed':
@@ -409,8 +452,9 @@ def c5_result(args, quick=False):
         def shape(R, t):
             o, d = ray_fn(7, R)
             ro, rd = T(o), T(d)
-            gd, gs, gc, gl = (torch.randn(R, device=dev), torch.randn(R, 17, device=dev), torch.randn(R, 3, device=dev),
-                              torch.randn(R, device=dev))
+            g = torch.Generator(device=dev).manual_seed(0)
+            gd, gs, gc, gl = (torch.randn(R, device=dev, generator=g), torch.randn(R, 17, device=dev, generator=g),
+                              torch.randn(R, 3, device=dev, generator=g), torch.randn(R, device=dev, generator=g))
             gg = torch.zeros_like(grid)
             dbg = ops.render_rays(ro, rd, t, grid, consts, want_debug=True)
             stats = dict(terminated_frac=round(float((dbg['alphainv_last'] < 1e-3).float().mean()), 4),
@@ -420,24 +464,29 @@ def c5_result(args, quick=False):
                 ops.render_rays(ro, rd, t, grid, consts)
 
             def fwd_bwd():
-                ops.render_rays(ro, rd, t, grid, consts)
+                out = ops.render_rays(ro, rd, t, grid, consts)
                 gg.zero_()
                 ops.render_rays_backward(ro, rd, t, grid, consts, gd, gs, gc, gl, grad_grid=gg)
+                return dict(out, grad_grid=gg)
             return fwd, fwd_bwd, (lambda: ops.render_rays(ro, rd, t, g16, consts)), stats
         fwd, fwd_bwd, fwd16, st = shape(3072, t96)
         t_end = time.perf_counter() + args.settle_s / 2
         while time.perf_counter() < t_end:
             fwd_bwd()
-        t_fb = timed(fwd_bwd, steps, args.warmup)
-        t_f, t_f16 = timed(fwd, steps, args.warmup), timed(fwd16, steps, args.warmup)
+        t_fb, out = timed(fwd_bwd, steps, args.warmup)
+        if name == 'mixed':
+            last.update(out)
+        t_f, t_f16 = timed(fwd, steps, args.warmup)[0], timed(fwd16, steps, args.warmup)[0]
         rf, rfb, _, st_ref = shape(38400, head.t_table(dev))
-        t_rf, t_rfb = timed(rf, 10, 2), timed(rfb, 5, 1)
+        t_rf, t_rfb = timed(rf, 10, 2)[0], timed(rfb, 5, 1)[0]
         return dict(st, forward_ms=round(t_f * 1e3, 4), forward_bf16_grid_ms=round(t_f16 * 1e3, 4), fwd_bwd_ms=round(t_fb * 1e3, 4),
                     rays_per_s_fwd_bwd=round(3072 / t_fb, 1), forward_samples_per_s=round(3072 * 96 / t_f, 0),
                     fwd_bwd_samples_per_s=round(3072 * 96 / t_fb, 0),
                     reference_shape_38400x417=dict(st_ref, forward_ms=round(t_rf * 1e3, 3), fwd_bwd_ms=round(t_rfb * 1e3, 3),
                                                    forward_samples_per_s=round(38400 * 417 / t_rf, 0))), grid.numel() * 4, t_f
     mixed, grid_bytes, t_f = scene('mixed')
+    dumped = dump_outputs(last, args.dump_outputs) if args.dump_outputs and not quick else None
+    last.clear()
     transparent, _, _ = scene('transparent')
     pretrain = pretrain_step_ms(dev, args)
     traffic, traffic_src = _pmc_traffic('k_render_rays')
@@ -461,6 +510,8 @@ def c5_result(args, quick=False):
                      'note': 'algorithmic bytes = the 61 MB packed grid read once per forward (SURVEY 8d); the kernel is bound by the '
                              'per-ray scan and gather latency, not by HBM (profiles/r02_render_c5.txt)'},
     }
+    if dumped is not None:
+        res['dump_outputs'] = dict(dir=args.dump_outputs, arrays=dumped)
     return res
 
 
@@ -746,7 +797,11 @@ def main():
     ap.add_argument('--no-d2h', action='store_true', help='leave the occupancy grids on the device (no host payload)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-extra', action='store_true', help='skip the compact C2 / C5 figures appended after the timed region')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last one computed to DIR/<name>.npy (rank 0; see dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.config == 'C5':
         return bench_c5(args)
 
@@ -798,12 +853,12 @@ def main():
 
     phase_ms, phase_bytes = {}, {}
     ss = None
+    ss_i = [0]
     if sharded and not args.no_graph:
         # round 6: the three compute phases between the two collectives as hipGraphs, ranges calibrated once + audited on the device
         from preworld_amd.pipeline import ShardedSample
         ss = ShardedSample(net, frames, ego, n_steps=n_steps_fc, gather_on_host=oversubscribed)
         ss_sets = [make_inputs(dev, seed=4000 + j, n_frames=n_frames) for j in range(3)]        # the same 3 samples on every rank, rotating
-        ss_i = [0]
 
     def step():
         if ss is not None:
@@ -871,18 +926,22 @@ def main():
         sets = [make_inputs(dev, seed=1000 + rank * 16 + j, n_frames=n_frames) for j in range(N_SETS)]
 
         def run_steps(n, rotate=True):
+            res = None
             for i in range(n):
                 with torch.cuda.stream(streams[i % M]):
                     if rotate:
-                        caps[i % M].run(*sets[i % N_SETS])
+                        res = caps[i % M].run(*sets[i % N_SETS])
                     else:
-                        caps[i % M].replay()
+                        res = caps[i % M].replay()
+            return res
     else:
         M = 1
 
         def run_steps(n, rotate=True):
+            res = None
             for _ in range(n):
-                step()
+                res = step()
+            return res
 
     t_settle = time.perf_counter() + args.settle_s
     while time.perf_counter() < t_settle:
@@ -900,8 +959,9 @@ def main():
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
+    ss_i[0] = 0                     # the run-in above is timed by the clock: restart the rotation so every run times the same samples
     t0 = time.perf_counter()
-    run_steps(args.steps)
+    last = run_steps(args.steps)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -910,6 +970,9 @@ def main():
         t = torch.tensor([elapsed], device='cpu' if oversubscribed else dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # before anything else runs: the captured steps' outputs are static buffers that the next replay overwrites
+    dumped = dump_outputs(last, args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    del last
 
     replay_only = None
     audit = None
@@ -1034,6 +1097,8 @@ def main():
             },
             'roofline': roofline,
         }
+        if dumped is not None:
+            res['dump_outputs'] = dict(dir=args.dump_outputs, arrays=dumped)
         if world == 1 and not sharded and args.config == 'C3' and not args.no_extra:
             res['extra'] = extra_figures(args, dev)
         if not args.no_cpu_baseline and world == 1 and not sharded:
