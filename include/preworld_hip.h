@@ -402,6 +402,16 @@ int pw_attr_mlp(const float* v0, int64_t n_vox, const float* w1p, const float* w
 int pw_confusion_hist(const uint8_t* pred, const uint8_t* gt, const uint8_t* mask, int64_t n,
                       int n_cl, int64_t* hist, void* stream);
 
+/* A22b  one sample's occupancy scores for n_h <= 8 horizons in ONE launch (mmdet3d/datasets/occ_metrics.py:82-105 hist_info,
+ * :135-158 add_batch, :502-542 the temporal evaluate loop).  pred_host / gt_host / mask_host: host arrays of n_h device pointers to
+ * uint8[n] grids (mask_host NULL, or an entry NULL: every voxel counts; mask != 0 selects).  counts int64[n_h][n_cl*n_cl + 4]
+ * ACCUMULATES: the first n_cl^2 entries are hist_info's bincount(n_cl*gt + pred) over masked voxels with gt < n_cl (and pred < n_cl),
+ * the last 4 the binary histogram [2*(gt != free) + (pred != free)], free = n_cl - 1, over masked voxels -- a gt of 255 counts as
+ * occupied there, as in the reference.  2 <= n_cl <= 32, n <= 2^31 - 1.  The pointers travel by value in the kernel arguments
+ * (capturable into a hipGraph). */
+int pw_occ_score(const uint8_t* const* pred_host, const uint8_t* const* gt_host, const uint8_t* const* mask_host, int n_h,
+                 int64_t n, int n_cl, int64_t* counts, void* stream);
+
 /* nn.Softplus(beta=1, threshold=20) elementwise (the activation inside fusion_head and the
  * attribute MLPs, preworld_temporal_traj.py:81-132), same device function as the fused kernels. */
 int pw_softplus(const float* x, float* y, int64_t n, void* stream);

@@ -164,3 +164,34 @@ def simple_test_sharded(net, frames, ego, n_steps=6, group=None, gather_on_host=
         for (_, a), (name, b) in zip(events[:-1], events[1:]):
             timings[name] = a.elapsed_time(b)
     return {'semantic_occ_%ds' % k: [g] for k, g in enumerate(grids)}
+
+
+@torch.no_grad()
+def evaluate_stream(net, samples, in_flight=2, use_image_mask=True, keep_stacks=False):
+    """harness.evaluate through pipeline.SampleStream: `in_flight` captured samples on their own HIP streams, every replay
+    range-checked, each sample scored on the device by one pw_occ_score launch inside its graph (no per-sample D2H copy).
+    samples: a list or iterable of the same dicts as evaluate (the first one fixes the shapes the graphs are captured for).
+    Returns what evaluate returns: (report, stacks or None, metric) -- stacks (the {0,2,4,6} stack per sample, numpy) only when
+    keep_stacks=True, which turns the payload copy on."""
+    from .pipeline import SampleStream
+    it = iter(samples)
+    first = next(it, None)
+    if first is None:
+        raise ValueError('evaluate_stream: no samples')
+    horizons = (0, 2, 4, 6)
+    stream = SampleStream(net, first['frames'], first['ego'], in_flight=in_flight, n_steps=6, payload=keep_stacks,
+                          score=dict(horizons=horizons, n_cl=18, mask='camera' if use_image_mask else None))
+    stacks = [] if keep_stacks else None
+    try:
+        for res in stream.run(_chain(first, it)):
+            if keep_stacks:
+                stacks.append(np.stack([res['semantic_occ_%ds' % h][0] for h in horizons], axis=0))
+        torch.cuda.current_stream().synchronize()
+    finally:
+        stream.close()
+    return stream.metric.report(), stacks, stream.metric
+
+
+def _chain(first, rest):
+    yield first
+    yield from rest

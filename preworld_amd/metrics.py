@@ -49,6 +49,17 @@ class Metric_mIoU:
         free = self.num_classes - 1
         ops.confusion_hist((p != free).to(torch.uint8), (g != free).to(torch.uint8), m, 2, self._occ_hist)
 
+    def add_counts(self, counts, n=1):
+        """add_batch's effect from a device table of n samples' scores: counts (n_cl*n_cl + 4,) or (1, n_cl*n_cl + 4) int64, the
+        confusion matrix then the binary 2x2 histogram (ops.occ_score / pw_occ_score).  hist, occ_hist and cnt then equal what
+        add_batch gives on the same grids.  Device-side adds on the current stream: no host sync."""
+        nb = self.num_classes * self.num_classes
+        c = counts.reshape(-1)
+        if c.numel() != nb + 4 or c.dtype != torch.int64:
+            raise ValueError('add_counts: expected %d int64 entries, got %d %s' % (nb + 4, c.numel(), c.dtype))
+        torch._foreach_add_([self._hist.view(-1), self._occ_hist.view(-1)], [c[:nb], c[nb:]])
+        self.cnt += int(n)
+
     @staticmethod
     def per_class_iu(hist):
         with np.errstate(divide='ignore', invalid='ignore'):
@@ -109,6 +120,25 @@ class Metric_mIoU_Temporal:
             self.add_idx(semantics_pred, semantics_gt_temp[idx],
                          mask_lidar_temp[idx] if mask_lidar_temp is not None else None,
                          mask_camera_temp[idx] if mask_camera_temp is not None else None, idx)
+
+    def add_counts(self, counts, n=1, horizons=None):
+        """add_batch's effect from a device table (len(horizons), n_cl*n_cl + 4) int64 of n samples' scores (ops.occ_score; row j
+        scores ground-truth index horizons[j], default (0, 2, 4, 6)): hist_*s, occ_hist_*s, cnt, count_miou(), count_iou() and
+        report() then equal what add_batch gives on the same stacks."""
+        horizons = self.horizons if horizons is None else tuple(horizons)
+        if counts.shape[0] != len(horizons) or any(h not in self.metrics for h in horizons):
+            raise ValueError('add_counts: one row per horizon of %s, got %s rows for %s' % (self.horizons, counts.shape[0], horizons))
+        nb = self.num_classes * self.num_classes
+        if counts.dtype != torch.int64 or counts.reshape(len(horizons), -1).shape[1] != nb + 4:
+            raise ValueError('add_counts: expected (%d, %d) int64, got %s %s' % (len(horizons), nb + 4, tuple(counts.shape), counts.dtype))
+        dst, src = [], []
+        for j, h in enumerate(horizons):                  # one multi-tensor add for every horizon's two histograms
+            m = self.metrics[h]
+            dst += [m._hist.view(-1), m._occ_hist.view(-1)]
+            src += [counts[j].reshape(-1)[:nb], counts[j].reshape(-1)[nb:]]
+            m.cnt += int(n)
+        torch._foreach_add_(dst, src)
+        self.cnt += int(n)
 
     def _miou(self, h):
         iu = Metric_mIoU.per_class_iu(self.metrics[h].hist)

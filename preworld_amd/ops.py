@@ -1416,3 +1416,38 @@ def confusion_hist(pred, gt, mask, n_cl, hist):
     _lib.call('pw_confusion_hist', _chk(p, torch.uint8, 'pred'), _chk(g, torch.uint8, 'gt'), _p(m),
               p.numel(), int(n_cl), _chk(hist, _i64, 'hist'), _stream())
     return hist
+
+
+OCC_SCORE_MAX_H = 8
+
+
+def occ_score_bins(n_cl):
+    """entries per horizon of an occ_score table: the n_cl x n_cl confusion matrix, then the binary 2x2 histogram"""
+    return int(n_cl) * int(n_cl) + 4
+
+
+def occ_score(preds, gts, masks, n_cl, counts):
+    """counts (H, n_cl*n_cl + 4) int64 += one sample's scores for H <= 8 horizons in ONE launch (pw_occ_score): per horizon h the
+    confusion matrix of occ_metrics.py:82-105 over masked voxels with gt < n_cl, then the binary free / occupied 2x2 histogram of
+    occ_metrics.py:150-154 (gt = 255 counts as occupied there).  preds / gts: H contiguous uint8 device grids of one voxel count;
+    masks: None or H uint8 / bool device grids (an entry None: no mask for that horizon).  Capturable: the pointers travel by value."""
+    H = len(preds)
+    if H < 1 or H > OCC_SCORE_MAX_H or len(gts) != H or (masks is not None and len(masks) != H):
+        raise _lib.PreworldHipError('occ_score: 1 <= H <= %d horizons, one gt (and mask) per prediction' % OCC_SCORE_MAX_H)
+    n = preds[0].numel()
+    if any(t.numel() != n for t in list(preds) + list(gts) + [m for m in (masks or ()) if m is not None]):
+        raise _lib.PreworldHipError('occ_score: every grid must hold the same number of voxels')
+    if tuple(counts.shape) != (H, occ_score_bins(n_cl)):
+        raise _lib.PreworldHipError('occ_score: counts must be (H, n_cl*n_cl + 4) = (%d, %d), got %s'
+                                    % (H, occ_score_bins(n_cl), tuple(counts.shape)))
+    keep = [_chk(p, torch.uint8, 'pred') for p in preds] + [_chk(g, torch.uint8, 'gt') for g in gts]
+    P = (ctypes.c_void_p * H)(*[p.value for p in keep[:H]])
+    G = (ctypes.c_void_p * H)(*[g.value for g in keep[H:]])
+    M = None
+    if masks is not None:
+        ms = [None if m is None else _chk(m.view(torch.uint8) if m.dtype == torch.bool else m, torch.uint8, 'mask') for m in masks]
+        keep += [m for m in ms if m is not None]
+        M = (ctypes.c_void_p * H)(*[None if m is None else m.value for m in ms])
+    _lib.call('pw_occ_score', P, G, M, H, n, int(n_cl), _chk(counts, _i64, 'counts'), _stream())
+    del keep
+    return counts

@@ -6,6 +6,8 @@ PreWorld4DTraj.simple_test (mmdet3d/models/detectors/preworld_temporal_traj.py:2
 static input/output buffers: a replay has no launch gaps (kernel time == wall time in
 profiles/r01_bench_kernel_stats_v5.md) and no per-launch host work, which is what the C3 step needs
 once the kernels themselves run in 10-1000 us."""
+import collections
+
 import numpy as np
 import torch
 
@@ -327,3 +329,298 @@ class ShardedSample:
         """(passes that left their calibrated activation ranges, passes audited) since capture (synchronises)"""
         torch.cuda.synchronize()
         return self.rctx.audited()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Streaming evaluation: M captured samples in flight, every replay range-checked, scored on the device, results in input order.
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+class StreamScheduler:
+    """The ordering / lag / repair / count logic of SampleStream over a list of slots (any objects with the methods below), so
+    that it can be pinned without a GPU.  Sample i goes to slot i % M; before a slot takes a new sample the host waits for THAT
+    slot's previous sample only, checks its ranges, repairs it if needed, commits its scores, enqueues the new sample and only
+    then hands the finished result out -- so results come out in input order, M - 1 samples behind the enqueue.
+
+    slot.stage(sample)   host-side preparation that does not touch the slot's device buffers (e.g. pinned staging of host GT)
+    slot.load(sample)    enqueue the copies of the sample's inputs into the slot's static buffers
+    slot.launch(buf)     enqueue one replay over the static buffers (+ the payload copy into host buffer `buf` of 2)
+    slot.wait()          host waits for the slot's last launch
+    slot.ranges_ok()     did the last replay stay inside its calibrated activation ranges?
+    slot.recalibrate()   re-derive the ranges from the inputs in the static buffers
+    slot.commit()        add the last replay's per-sample score table to the running totals
+    slot.result(buf)     what run() yields for the sample (valid at least until the next next())"""
+
+    def __init__(self, slots):
+        self.slots = list(slots)
+        self.replays = 0
+        self.recalibrations = 0
+
+    def run(self, samples):
+        M = len(self.slots)
+        pending = collections.deque()               # (slot, payload buffer, sample): the sample stays referenced until it is finished
+        parity = [0] * M
+        for i, sample in enumerate(samples):
+            s = i % M
+            slot = self.slots[s]
+            slot.stage(sample)
+            done = self._finish(*pending.popleft()) if len(pending) == M else None      # the oldest in flight sits in slot s
+            slot.load(sample)
+            slot.launch(parity[s])
+            self.replays += 1
+            pending.append((slot, parity[s], sample))
+            parity[s] ^= 1
+            if done is not None:
+                yield done
+        while pending:
+            yield self._finish(*pending.popleft())
+
+    def _finish(self, slot, buf, sample):
+        slot.wait()
+        if not slot.ranges_ok():
+            # a replay outside its window is never counted: repair, replay the same static inputs, check again (run_checked)
+            self.recalibrations += 1
+            slot.recalibrate()
+            slot.launch(buf)
+            self.replays += 1
+            slot.wait()
+            if not slot.ranges_ok():
+                raise ops._lib.PreworldHipError('activation ranges still outside the window after recalibration')
+        slot.commit()
+        return slot.result(buf)
+
+
+class _ScoredCapture(CapturedSample):
+    """CapturedSample whose graph also scores the sample: static GT / mask buffers (one row per scored horizon) and one
+    pw_occ_score launch that zeroes, then fills the slot's per-sample table.  payload: the device rows of the host payload
+    (the OccHead's in-place `grids` rows when the layout allows, else a gather inside the graph), copied out by the stream."""
+
+    def __init__(self, net, frames, ego, n_steps, pred_keys=None, n_cl=18, masked=False, payload=False):
+        self.pred_keys, self.n_cl, self.masked, self.want_payload = pred_keys, n_cl, masked, payload
+        self.gt = self.mask = self.table = None
+        self.payload_dev = self.payload_keys = None
+        super().__init__(net, frames, ego, n_steps=n_steps, d2h=False)
+
+    def _step(self):
+        out = super()._step()
+        capturing = torch.cuda.is_current_stream_capturing()
+        if self.want_payload and capturing:
+            keys = [k for k in out if k.startswith(('semantic_occ', 'geo_occ'))]
+            g = out.get('grids')
+            if g is not None and g.numel() == len(keys) * out[keys[0]][0].numel() and all(
+                    out[k][0].data_ptr() == g.data_ptr() + i * out[k][0].numel() for i, k in enumerate(keys)):
+                self.payload_dev = g.view((len(keys),) + tuple(out[keys[0]][0].shape))
+            else:
+                self.payload_dev = torch.stack([out[k][0] for k in keys])
+            self.payload_keys = keys
+        if self.pred_keys:
+            preds = [out[k][0] if out[k][0].is_contiguous() else out[k][0].contiguous() for k in self.pred_keys]
+            if self.gt is None:                       # first (eager, uncaptured) pass: the static buffers take the grid shape
+                H, shape, dev = len(preds), tuple(preds[0].shape), preds[0].device
+                self.gt = torch.zeros((H,) + shape, dtype=torch.uint8, device=dev)
+                self.mask = torch.ones((H,) + shape, dtype=torch.uint8, device=dev) if self.masked else None
+                self.table = torch.zeros((H, ops.occ_score_bins(self.n_cl)), dtype=torch.int64, device=dev)
+            self.table.zero_()
+            ops.occ_score(preds, list(self.gt), list(self.mask) if self.mask is not None else None, self.n_cl, self.table)
+        return out
+
+
+def _grid_per_horizon(v, horizons):
+    """a sample's gt / mask entry: {h: grid} or one grid for every horizon"""
+    return [v[h] for h in horizons] if isinstance(v, dict) else [v] * len(horizons)
+
+
+class _StreamSlot:
+    """one slot of SampleStream: a _ScoredCapture on its own HIP stream, pinned staging for host GT, two pinned payload buffers"""
+
+    def __init__(self, owner, cap):
+        self.owner, self.cap = owner, cap
+        self.stream = torch.cuda.Stream(device=cap.ego.device)
+        self.done = torch.cuda.Event()
+        self.staged = torch.cuda.Event()              # the H2D copies out of the staging buffers have been enqueued before this
+        self.host = self.views = None
+        if cap.payload_dev is not None:
+            self.host = [torch.empty(tuple(cap.payload_dev.shape), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+            self.views = [{k: [h[i].numpy()] for i, k in enumerate(cap.payload_keys)} for h in self.host]
+        self.stage_gt = self.stage_mask = None
+        self._host_rows = ()
+
+    def _grids(self, sample):
+        """(kind, row, array) of the sample's GT (and mask) per scored horizon"""
+        hz = self.owner.horizons
+        out = [('gt', j, a) for j, a in enumerate(_grid_per_horizon(sample['gt'], hz))]
+        if self.cap.mask is not None:
+            m = sample.get(self.owner.mask_key)
+            if m is None:                             # no mask with this sample: every voxel counts (as add_batch with None)
+                m = np.ones(tuple(self.cap.mask.shape[1:]), dtype=np.uint8)
+            out += [('mask', j, a) for j, a in enumerate(_grid_per_horizon(m, hz))]
+        return out
+
+    def stage(self, sample):
+        """host GT / masks -> this slot's pinned staging, once the previous sample's H2D copies out of it have completed"""
+        rows = []
+        if self.cap.table is not None:
+            for kind, j, a in self._grids(sample):
+                if isinstance(a, torch.Tensor) and a.is_cuda:
+                    continue
+                if not rows:
+                    self.staged.synchronize()
+                    if self.stage_gt is None:
+                        self.stage_gt = torch.empty(tuple(self.cap.gt.shape), dtype=torch.uint8, pin_memory=True)
+                        self.stage_mask = torch.empty(tuple(self.cap.gt.shape), dtype=torch.uint8, pin_memory=True)
+                dst = (self.stage_gt if kind == 'gt' else self.stage_mask)[j]
+                np.copyto(dst.numpy(), np.asarray(a).reshape(tuple(dst.shape)), casting='unsafe')
+                rows.append((kind, j))
+        self._host_rows = tuple(rows)
+
+    def load(self, sample):
+        cap, st = self.cap, self.stream
+        st.wait_stream(torch.cuda.current_stream())   # the sample's device tensors were made on the caller's stream
+        dsts, srcs = ([cap.ego], [sample['ego']]) if self.owner.temporal else ([], [])
+        for dst, src in zip(cap.frames, sample['frames']):
+            for k, v in src.items():
+                dsts.append(dst[k])
+                srcs.append(v)
+        if cap.table is not None:
+            for kind, j, a in self._grids(sample):
+                if isinstance(a, torch.Tensor) and a.is_cuda:
+                    dsts.append((cap.gt if kind == 'gt' else cap.mask)[j])
+                    srcs.append(a.view(torch.uint8) if a.dtype == torch.bool else a)
+        with torch.cuda.stream(st):
+            # CapturedSample.run's guard: one pw_copy_many launch when every source qualifies, else one copy per tensor
+            if cap.fused_input_copy and all(s_.is_cuda and s_.is_contiguous() and s_.dtype == d.dtype and s_.shape == d.shape
+                                            for d, s_ in zip(dsts, srcs)):
+                ops.copy_many(dsts, srcs)
+            else:
+                for d, s_ in zip(dsts, srcs):
+                    d.copy_(s_, non_blocking=True)
+            for kind, j in self._host_rows:
+                (cap.gt if kind == 'gt' else cap.mask)[j].copy_((self.stage_gt if kind == 'gt' else self.stage_mask)[j], non_blocking=True)
+            if self._host_rows:
+                self.staged.record(st)
+        self._host_rows = ()
+
+    def launch(self, buf):
+        with torch.cuda.stream(self.stream):
+            self.cap.replay()
+            if self.host is not None:
+                self.host[buf].copy_(self.cap.payload_dev, non_blocking=True)
+            self.done.record(self.stream)
+
+    def wait(self):
+        self.done.synchronize()
+
+    def ranges_ok(self):
+        return self.cap.ranges_ok()
+
+    def recalibrate(self):
+        self.cap.recalibrate()
+
+    def commit(self):
+        if self.cap.table is None:
+            return
+        ms = self.owner.metric_stream
+        with torch.cuda.stream(ms):
+            if self.owner.temporal:
+                self.owner.metric.add_counts(self.cap.table, 1, horizons=self.owner.horizons)
+            else:
+                self.owner.metric.add_counts(self.cap.table, 1)
+        self.stream.wait_stream(ms)                   # the next replay re-zeroes the table: after the add
+
+    def result(self, buf):
+        return dict(self.views[buf]) if self.views is not None else {}
+
+
+class SampleStream:
+    """Streaming inference + evaluation through the captured hot path: `in_flight` slots, each a hipGraph of one sample
+    (CapturedSample over static buffers) on its own HIP stream.  run(samples) yields one result per sample, in input order:
+
+    * payload=True: {'semantic_occ_{k}s' / 'geo_occ_{k}s' (PreWorld: 'semantic_occ' / 'geo_occ'): [numpy uint8 (X,Y,Z)]} -- views
+      of pinned buffers, valid until the next next() (copy what you keep); payload=False: {} (no device-to-host copy at all);
+    * score=dict(horizons=(0, 2, 4, 6), n_cl=18, mask='camera' | 'lidar' | None[, metric=...]): the graph also holds static GT /
+      mask buffers and one pw_occ_score launch, and every finished sample's table is added to `self.metric` on the device
+      (Metric_mIoU_Temporal for PreWorld4DTraj, Metric_mIoU with horizons (0,) for PreWorld) -- no per-sample result comes back to
+      the host.  Samples then carry gt={h: (X,Y,Z) uint8} (or one grid) and mask_camera / mask_lidar (one grid or {h: grid}), numpy
+      (through pinned staging) or device tensors.
+
+    Every replay is range-checked before it counts (a miss: recalibrate, replay the same inputs, check again; still outside the
+    window -> PreworldHipError).  Counters: `replays`, `recalibrations`, `recaptures`.
+    Stale captures: a fingerprint -- precision() and (data_ptr, _version) of every parameter and buffer -- is taken at capture and
+    compared at the start of every run(); a change (load_state_dict, an in-place update) re-captures.  Writes through `.data`
+    bypass the version counter and are NOT seen: call recapture() after them.
+    close() frees the graphs and static buffers (about 1.5 GB per full-size C3 slot)."""
+
+    def __init__(self, net, example_frames, example_ego=None, in_flight=2, n_steps=6, payload=True, score=None):
+        from . import metrics
+        self.net, self.in_flight, self.payload = net, max(1, int(in_flight)), payload
+        self.temporal = hasattr(net, 'forecast_cl')
+        self.n_steps = n_steps if self.temporal else 0
+        self.example = (example_frames, example_ego if self.temporal else example_frames[0]['bda'].new_zeros(1))
+        if self.temporal and example_ego is None:
+            raise ValueError('SampleStream: PreWorld4DTraj needs example ego states (B,1,21)')
+        self.score = dict(score) if score is not None else None
+        self.metric = None
+        self.horizons, self.mask_key, self.pred_keys = (), None, None
+        if self.score is not None:
+            self.horizons = tuple(self.score.get('horizons', (0, 2, 4, 6) if self.temporal else (0,)))
+            n_cl = self.score.setdefault('n_cl', 18)
+            mask = self.score.get('mask', 'camera')
+            self.mask_key = {'camera': 'mask_camera', 'lidar': 'mask_lidar', None: None}[mask]
+            if self.temporal:
+                self.pred_keys = ['semantic_occ_%ds' % h for h in self.horizons]
+                if any(h > self.n_steps for h in self.horizons):
+                    raise ValueError('SampleStream: horizons %s beyond n_steps %d' % (self.horizons, self.n_steps))
+            else:
+                if self.horizons != (0,):
+                    raise ValueError('SampleStream: PreWorld predicts one state, horizons must be (0,)')
+                self.pred_keys = ['semantic_occ']
+            self.metric = self.score.get('metric')
+            if self.metric is None:
+                dev = self.example[1].device
+                kw = dict(num_classes=n_cl, use_image_mask=mask == 'camera', use_lidar_mask=mask == 'lidar', device=dev)
+                self.metric = metrics.Metric_mIoU_Temporal(**kw) if self.temporal else metrics.Metric_mIoU(**kw)
+        self.replays = self.recalibrations = self.recaptures = 0
+        self.slots = []
+        self.metric_stream = None
+        self._fp = None
+        self._capture()
+
+    def _fingerprint(self):
+        from .modules import precision
+        ts = list(self.net.parameters()) + list(self.net.buffers())
+        return (precision(),) + tuple((t.data_ptr(), t._version) for t in ts)
+
+    def _capture(self):
+        self.close()
+        frames, ego = self.example
+        kw = dict(pred_keys=self.pred_keys, n_cl=self.score['n_cl'] if self.score else 18, masked=self.mask_key is not None,
+                  payload=self.payload)
+        self.slots = [_StreamSlot(self, _ScoredCapture(self.net, frames, ego, self.n_steps, **kw)) for _ in range(self.in_flight)]
+        self._fp = self._fingerprint()
+
+    def recapture(self):
+        """capture every slot again (what run() does by itself when the fingerprint changed)"""
+        self._capture()
+        self.recaptures += 1
+
+    def run(self, samples):
+        if not self.slots:
+            raise RuntimeError('SampleStream: closed')
+        if self._fingerprint() != self._fp:
+            self.recapture()
+        self.metric_stream = torch.cuda.current_stream() if self.metric is not None else None     # where the totals are added
+        sched = StreamScheduler(self.slots)
+        try:
+            for r in sched.run(samples):
+                yield r
+        finally:
+            self.replays += sched.replays
+            self.recalibrations += sched.recalibrations
+
+    def close(self):
+        """free the graphs and the static buffers of every slot"""
+        if self.slots:
+            torch.cuda.synchronize()
+            for sl in self.slots:
+                sl.cap.graph.reset()
+            self.slots = []
+            torch.cuda.empty_cache()

@@ -1,0 +1,121 @@
+"""Throughput of streaming evaluation (pipeline.SampleStream) at C3 against bench.py's raw captured loop, in one process.
+
+    python tools/bench_stream.py [--in-flight 2] [--samples 600] [--warmup 20] [--eval-samples 100]
+
+Prints one JSON line with samples/s for
+  raw        bench.py's timed loop restated: M CapturedSamples (host payload in the graph, as bench.py's default), rotating
+             resident input sets, each replayed on its own stream, nothing checked, nothing scored
+  score      SampleStream(payload=False, score=...): every replay range-checked, scored in the graph, no D2H
+  payload    SampleStream(payload=True, score=...): the same plus the 14-grid host payload per sample
+  evaluate   harness.evaluate (eager, one sample at a time, host-side stacking) on the same samples
+raw, score and payload alternate (twice each, about 1.5 s per window at C3) so drift shows; the ratios use the means.
+Inputs, GT grids and masks are resident in HBM (N_SETS distinct samples from fixed seeds); evaluate gets the GT as numpy, as
+its callers pass it."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import bench  # noqa: E402
+from preworld_amd import harness  # noqa: E402
+from preworld_amd.pipeline import CapturedSample, SampleStream  # noqa: E402
+
+N_SETS = 5
+HZ = (0, 2, 4, 6)
+
+
+def make_samples(dev, n_frames):
+    rs = np.random.RandomState(2024)
+    out = []
+    for j in range(N_SETS):
+        frames, ego = bench.make_inputs(dev, seed=1000 + j, n_frames=n_frames)
+        gt = {h: rs.randint(0, 18, size=(200, 200, 16)).astype(np.uint8) for h in HZ}
+        mask = rs.rand(200, 200, 16) < 0.7
+        out.append(dict(frames=frames, ego=ego, gt_np=gt, mask_np=mask,
+                        gt={h: torch.from_numpy(g).to(dev) for h, g in gt.items()},
+                        mask_camera=torch.from_numpy(mask).to(dev)))
+    return out
+
+
+def time_raw(caps, streams, sets, n):
+    M = len(caps)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(n):
+        with torch.cuda.stream(streams[i % M]):
+            caps[i % M].run(sets[i % N_SETS]['frames'], sets[i % N_SETS]['ego'])
+    torch.cuda.synchronize()
+    return n / (time.perf_counter() - t0)
+
+
+def time_stream(st, sets, n):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    k = 0
+    for _ in st.run(sets[i % N_SETS] for i in range(n)):
+        k += 1
+    torch.cuda.synchronize()
+    assert k == n
+    return n / (time.perf_counter() - t0)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--in-flight', type=int, default=2)
+    ap.add_argument('--samples', type=int, default=600)
+    ap.add_argument('--warmup', type=int, default=20)
+    ap.add_argument('--eval-samples', type=int, default=100)
+    args = ap.parse_args()
+    dev = 'cuda:0'
+    M = max(1, args.in_flight)
+    net, _ = bench.build_net(dev, 'C3')
+    n_frames = 2
+    sets = make_samples(dev, n_frames)
+    score = dict(horizons=HZ, n_cl=18, mask='camera')
+
+    caps = [CapturedSample(net, *bench.make_inputs(dev, seed=k, n_frames=n_frames), n_steps=6, d2h=True) for k in range(M)]
+    streams = [torch.cuda.Stream() for _ in range(M)]
+    st_b = SampleStream(net, sets[0]['frames'], sets[0]['ego'], in_flight=M, payload=False, score=score)
+    st_c = SampleStream(net, sets[0]['frames'], sets[0]['ego'], in_flight=M, payload=True, score=score)
+    time_raw(caps, streams, sets, args.warmup)
+    time_stream(st_b, sets, args.warmup)
+    time_stream(st_c, sets, args.warmup)
+    raw, sc, pay = [], [], []
+    for _ in range(2):                                  # alternating, so that drift of the machine shows in both
+        raw.append(time_raw(caps, streams, sets, args.samples))
+        sc.append(time_stream(st_b, sets, args.samples))
+        pay.append(time_stream(st_c, sets, args.samples))
+    bad = [c.bad_replays() for c in caps]
+    del caps
+    res = dict(config='C3', in_flight=M, samples_timed=args.samples, raw_samples_per_s=[round(v, 1) for v in raw],
+               score_samples_per_s=[round(v, 1) for v in sc], payload_samples_per_s=[round(v, 1) for v in pay])
+    counters = {name: dict(replays=st.replays, recalibrations=st.recalibrations) for name, st in (('score', st_b), ('payload', st_c))}
+    st_b.close()
+    st_c.close()
+
+    ev_samples = [dict(frames=s['frames'], ego=s['ego'], gt=s['gt_np'], mask_camera=s['mask_np'])
+                  for s in (sets[i % N_SETS] for i in range(args.eval_samples))]
+    harness.evaluate(net, ev_samples[:2], dev)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    harness.evaluate(net, ev_samples, dev)
+    torch.cuda.synchronize()
+    ev = args.eval_samples / (time.perf_counter() - t0)
+
+    a, b, c = float(np.mean(raw)), float(np.mean(sc)), float(np.mean(pay))
+    res.update(evaluate_samples_per_s=round(ev, 1), evaluate_samples_timed=args.eval_samples,
+               ratio_score_over_raw=round(b / a, 4), ratio_payload_over_raw=round(c / a, 4),
+               raw_bad_replays=[list(x) for x in bad], counters=counters,
+               gt_resident=True, torch=torch.__version__, pw_precision=os.environ.get('PW_PRECISION', 'h2'))
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == '__main__':
+    main()
