@@ -412,6 +412,26 @@ int pw_confusion_hist(const uint8_t* pred, const uint8_t* gt, const uint8_t* mas
 int pw_occ_score(const uint8_t* const* pred_host, const uint8_t* const* gt_host, const uint8_t* const* mask_host, int n_h,
                  int64_t n, int n_cl, int64_t* counts, void* stream);
 
+/* A22c  one sample's occupancy F-score counts for n_h <= 8 horizons in ONE launch (mmdet3d/datasets/occ_metrics.py:322-410
+ * Metric_FScore: :352-363 voxel2points, :365-397 add_batch's two KDTree queries, restated exactly as a lattice stencil).
+ * pred_host / gt_host / mask_host: host arrays of n_h device pointers to uint8 (X, Y, Z) grids, z fastest (mask_host NULL, or
+ * an entry NULL: no mask; where mask == 0 pred and gt read as 255, :372-378).  A voxel is occupied when its value v has bit v
+ * of void_bits[8] clear.  m_acc / m_cmpl: int8 [2rx + 1][2ry + 1] tables (ops.fscore_offsets): a voxel of the other grid at
+ * column offset (dx, dy) lies within the threshold iff |dz| <= m[dx + rx][dy + ry] (-1: no dz); neighbours outside the grid do
+ * not exist.  counts int64[n_h][4] ACCUMULATES {n_pred, n_pred_hit, n_gt, n_gt_hit}: occupied pred voxels, those with an
+ * occupied gt voxel within threshold_acc, occupied gt voxels, those with an occupied pred voxel within threshold_complete.
+ * Z <= 64, rx, ry <= 7, X*Y*Z <= 2^31 - 1.  Pointers and tables travel by value in the kernel arguments (capturable). */
+int pw_occ_fscore(const uint8_t* const* pred_host, const uint8_t* const* gt_host, const uint8_t* const* mask_host, int n_h,
+                  int X, int Y, int Z, const uint32_t* void_bits, const int8_t* m_acc, const int8_t* m_cmpl, int rx, int ry,
+                  int64_t* counts, void* stream);
+
+/* A22c  totals float64[n_h][3] += (accuracy, completeness, F1) of n_s samples' count tables int64[n_s][n_h][4] (pw_occ_fscore),
+ * in sample order, with the reference's float64 arithmetic (occ_metrics.py:380-408): acc = n_pred_hit / n_pred,
+ * cmpl = n_gt_hit / n_gt, f = 2 / (1 / (acc + 1e-8) + 1 / (cmpl + 1e-8)), uncontracted; (0, 0, 0) when n_pred == 0.  A sample
+ * with n_pred > 0 and n_gt == 0 (the reference raises inside KDTree) adds (0, 0, 0) and increments n_empty_gt[h] (int64[n_h]).
+ * One launch, 1 <= n_h <= 8. */
+int pw_occ_fscore_accumulate(const int64_t* counts, int n_s, int n_h, double* totals, int64_t* n_empty_gt, void* stream);
+
 /* nn.Softplus(beta=1, threshold=20) elementwise (the activation inside fusion_head and the
  * attribute MLPs, preworld_temporal_traj.py:81-132), same device function as the fused kernels. */
 int pw_softplus(const float* x, float* y, int64_t n, void* stream);

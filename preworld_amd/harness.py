@@ -72,13 +72,17 @@ def stack_states(result, horizons=(0, 2, 4, 6)):
 
 
 @torch.no_grad()
-def evaluate(net, samples, device='cuda:0', use_image_mask=True):
+def evaluate(net, samples, device='cuda:0', use_image_mask=True, fscore=None):
     """samples: iterable of dict(frames, ego, gt {idx: (X,Y,Z) uint8}, mask_camera (X,Y,Z) bool).
     Scores the stacked states {0,2,4,6} like tools/test_temporal.py -> dataset.evaluate
     (nuscenes_dataset_occ_trajectory.py:478-526).  Returns (Metric_mIoU_Temporal.report() dict incl. the 0 s horizon and
     'avg_future', list of stacked predictions); the reference's own return values are metric.count_miou() /
-    count_iou() of the same object (third return value)."""
+    count_iou() of the same object (third return value).
+    fscore: None, or a dict of Metric_FScore keyword arguments plus mask=None | 'camera' | 'lidar' (the sample entry it reads):
+    every horizon is also scored by a Metric_FScore (occ_metrics.py:322-410), report['fscore'] = {idx: tot_f1_mean / cnt} and
+    metric.fscore = {idx: Metric_FScore}."""
     metric = metrics.Metric_mIoU_Temporal(num_classes=18, use_image_mask=use_image_mask, device=device)
+    fs = _fscore_metrics(fscore, metric.horizons, device) if fscore is not None else None
     stacks = []
     for s in samples:
         res = net.simple_test_from_lift(s['frames'], s['ego'], n_steps=6)
@@ -86,7 +90,24 @@ def evaluate(net, samples, device='cuda:0', use_image_mask=True):
         stacks.append(st)
         mc = s.get('mask_camera')
         metric.add_batch(st, s['gt'], None, {h: mc for h in s['gt']} if mc is not None else None)
-    return metric.report(), stacks, metric
+        if fs is not None:
+            for h, f in fs.items():
+                ml, mc_ = s.get('mask_lidar'), s.get('mask_camera')
+                f.add_batch(st[h // 2], s['gt'][h], ml[h] if isinstance(ml, dict) else ml, mc_[h] if isinstance(mc_, dict) else mc_)
+    report = metric.report()
+    if fs is not None:
+        metric.fscore = fs
+        report['fscore'] = {h: f.tot_f1_mean / f.cnt for h, f in fs.items()}
+    return report, stacks, metric
+
+
+def _fscore_metrics(fscore, horizons, device):
+    kw = dict(fscore)
+    mask = kw.pop('mask', None)
+    if mask not in ('camera', 'lidar', None):
+        raise ValueError("fscore['mask'] must be 'camera', 'lidar' or None, got %r" % (mask,))
+    return {h: metrics.Metric_FScore(use_image_mask=mask == 'camera', use_lidar_mask=mask == 'lidar', device=device, **kw)
+            for h in horizons}
 
 
 @torch.no_grad()
@@ -167,20 +188,24 @@ def simple_test_sharded(net, frames, ego, n_steps=6, group=None, gather_on_host=
 
 
 @torch.no_grad()
-def evaluate_stream(net, samples, in_flight=2, use_image_mask=True, keep_stacks=False):
+def evaluate_stream(net, samples, in_flight=2, use_image_mask=True, keep_stacks=False, fscore=None):
     """harness.evaluate through pipeline.SampleStream: `in_flight` captured samples on their own HIP streams, every replay
     range-checked, each sample scored on the device by one pw_occ_score launch inside its graph (no per-sample D2H copy).
     samples: a list or iterable of the same dicts as evaluate (the first one fixes the shapes the graphs are captured for).
     Returns what evaluate returns: (report, stacks or None, metric) -- stacks (the {0,2,4,6} stack per sample, numpy) only when
-    keep_stacks=True, which turns the payload copy on."""
+    keep_stacks=True, which turns the payload copy on.
+    fscore: as for evaluate -- one more launch inside each sample's graph (pw_occ_fscore) and one fold per finished sample
+    (pw_occ_fscore_accumulate); then report['fscore'] = {idx: tot_f1_mean / cnt} and metric.fscore = {idx: Metric_FScore}."""
     from .pipeline import SampleStream
     it = iter(samples)
     first = next(it, None)
     if first is None:
         raise ValueError('evaluate_stream: no samples')
     horizons = (0, 2, 4, 6)
-    stream = SampleStream(net, first['frames'], first['ego'], in_flight=in_flight, n_steps=6, payload=keep_stacks,
-                          score=dict(horizons=horizons, n_cl=18, mask='camera' if use_image_mask else None))
+    score = dict(horizons=horizons, n_cl=18, mask='camera' if use_image_mask else None)
+    if fscore is not None:
+        score['fscore'] = dict(fscore)
+    stream = SampleStream(net, first['frames'], first['ego'], in_flight=in_flight, n_steps=6, payload=keep_stacks, score=score)
     stacks = [] if keep_stacks else None
     try:
         for res in stream.run(_chain(first, it)):
@@ -189,7 +214,11 @@ def evaluate_stream(net, samples, in_flight=2, use_image_mask=True, keep_stacks=
         torch.cuda.current_stream().synchronize()
     finally:
         stream.close()
-    return stream.metric.report(), stacks, stream.metric
+    report = stream.metric.report()
+    if fscore is not None:
+        stream.metric.fscore = stream.fscore
+        report['fscore'] = {h: f.tot_f1_mean / f.cnt for h, f in stream.fscore.items()}
+    return report, stacks, stream.metric
 
 
 def _chain(first, rest):

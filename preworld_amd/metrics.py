@@ -1,7 +1,8 @@
-"""Occupancy mIoU metrics -- drop-ins for mmdet3d/datasets/occ_metrics.py:52-185 (Metric_mIoU) and
-:413-594 (Metric_mIoU_Temporal): same constructor flags, add_batch / count_miou semantics.  The
+"""Occupancy metrics -- drop-ins for mmdet3d/datasets/occ_metrics.py:52-185 (Metric_mIoU), :322-410 (Metric_FScore) and
+:413-594 (Metric_mIoU_Temporal): same constructor flags, add_batch / count_miou / count_fscore semantics.  The
 18x18 confusion matrix is accumulated on the GPU (pw_confusion_hist, exact integer work); the
-final per-class IoU / nanmean is the reference's numpy arithmetic."""
+final per-class IoU / nanmean is the reference's numpy arithmetic.  The F-score's neighbour counts are a lattice stencil
+on the GPU (pw_occ_fscore) and its float64 totals are folded there with the reference's arithmetic."""
 import numpy as np
 import torch
 
@@ -164,3 +165,102 @@ class Metric_mIoU_Temporal:
         out = {h: self._miou(h)[1] for h in self.horizons}
         out['avg_future'] = round(float(np.mean([out[h] for h in self.horizons if h != 0])), 2)
         return out
+
+
+class Metric_FScore:
+    """Drop-in for occ_metrics.py:322-410 (the Occ3D geometry F-score): same constructor kwargs -- leaf_size is accepted and
+    ignored (there is no tree), range only places the reference's points and cannot change a distance -- plus device=.
+
+    * add_batch(semantics_pred, semantics_gt, mask_lidar, mask_camera): one (X, Y, Z) sample, numpy or device arrays.  The
+      counts come from one pw_occ_fscore launch (the KDTree queries of :383-397 restated exactly on the voxel lattice, see
+      ops.fscore_offsets) and one pw_occ_fscore_accumulate launch folds them into float64 device totals with the reference's
+      arithmetic, so tot_acc / tot_cmpl / tot_f1_mean are the same float64 sums.  Unlike the reference (:372-378), the
+      caller's arrays are NOT modified when a mask is used.
+    * add_counts(table): the same from a device count table (ops.occ_fscore), one row (4,) per sample.
+    * count_fscore() prints the reference's line and also returns the value.
+    * cnt, tot_acc, tot_cmpl, tot_f1_mean as in the reference (the totals are read from the device: a sync).
+    Deviation: a sample with an occupied prediction and an empty ground truth makes the reference raise inside KDTree; here it
+    adds (0, 0, 0) and is counted in n_empty_gt."""
+
+    def __init__(self, leaf_size=10, threshold_acc=0.6, threshold_complete=0.6, voxel_size=[0.4, 0.4, 0.4],
+                 range=[-40, -40, -1, 40, 40, 5.4], void=[17, 255], use_lidar_mask=False, use_image_mask=False,
+                 device='cuda:0', _totals=None, _empty=None):
+        self.leaf_size = leaf_size
+        self.threshold_acc = threshold_acc
+        self.threshold_complete = threshold_complete
+        self.voxel_size = voxel_size
+        self.range = range
+        self.void = void
+        self.use_lidar_mask = use_lidar_mask
+        self.use_image_mask = use_image_mask
+        self.device = device
+        self.cnt = 0
+        self.eps = 1e-8
+        ops.fscore_offsets(threshold_acc, voxel_size)             # a threshold that ties a lattice distance fails here
+        ops.fscore_offsets(threshold_complete, voxel_size)
+        self._totals = _totals if _totals is not None else torch.zeros(1, 3, dtype=torch.float64, device=device)
+        self._empty = _empty if _empty is not None else torch.zeros(1, dtype=torch.int64, device=device)
+        self._table = torch.zeros(1, 4, dtype=torch.int64, device=device)
+
+    @classmethod
+    def _group(cls, n, **kw):
+        """n metrics whose totals are the rows of one (n, 3) tensor: one pw_occ_fscore_accumulate launch adds a sample's
+        (n, 4) table to all of them (SampleStream).  Returns (metrics, totals, n_empty_gt)."""
+        dev = kw.get('device', 'cuda:0')
+        totals = torch.zeros(n, 3, dtype=torch.float64, device=dev)
+        empty = torch.zeros(n, dtype=torch.int64, device=dev)
+        return [cls(_totals=totals[j:j + 1], _empty=empty[j:j + 1], **kw) for j in range(n)], totals, empty
+
+    def kernel_args(self):
+        """the keyword arguments of ops.occ_fscore this metric scores with"""
+        return dict(void=tuple(self.void), voxel_size=tuple(self.voxel_size), thr_acc=self.threshold_acc,
+                    thr_cmpl=self.threshold_complete)
+
+    @property
+    def tot_acc(self):
+        return float(self._totals[0, 0].item())
+
+    @property
+    def tot_cmpl(self):
+        return float(self._totals[0, 1].item())
+
+    @property
+    def tot_f1_mean(self):
+        return float(self._totals[0, 2].item())
+
+    @property
+    def n_empty_gt(self):
+        """samples with an occupied prediction and no occupied ground truth (the reference raises on them)"""
+        return int(self._empty[0].item())
+
+    def add_batch(self, semantics_pred, semantics_gt, mask_lidar, mask_camera):
+        mask = mask_camera if self.use_image_mask else (mask_lidar if self.use_lidar_mask else None)
+        p = _dev(semantics_pred, self.device).to(torch.uint8).contiguous()
+        g = _dev(semantics_gt, self.device).to(torch.uint8).contiguous()
+        m = _dev(mask, self.device).to(torch.uint8).contiguous() if mask is not None else None
+        if p.dim() != 3:
+            raise ValueError('Metric_FScore.add_batch: expected one (X, Y, Z) grid, got %s' % (tuple(p.shape),))
+        self._table.zero_()
+        ops.occ_fscore([p], [g], [m] if m is not None else None, self._table, **self.kernel_args())
+        ops.occ_fscore_accumulate(self._table, self._totals, self._empty)
+        self.cnt += 1
+
+    def add_counts(self, table):
+        """add_batch's effect from a device count table of n samples (ops.occ_fscore rows {n_pred, n_pred_hit, n_gt, n_gt_hit}):
+        (4,), (1, 4), (n, 4) or (n, 1, 4) int64, one row per sample, folded in row order.  No host sync."""
+        if table.dtype != torch.int64 or table.numel() % 4 or table.shape[-1] != 4:
+            raise ValueError('add_counts: expected (n, 4) int64 rows, got %s %s' % (tuple(table.shape), table.dtype))
+        t = table.reshape(-1, 1, 4)
+        ops.occ_fscore_accumulate(t, self._totals, self._empty)
+        self.cnt += t.shape[0]
+
+    def count_fscore(self):
+        value = self.tot_f1_mean / self.cnt
+        line = '\n######## F score: {} #######'.format(value)
+        try:
+            from termcolor import colored
+            line = colored(line, 'red', attrs=['bold', 'dark'])
+        except ImportError:
+            pass
+        print(line)
+        return value

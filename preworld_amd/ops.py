@@ -5,8 +5,10 @@ All arithmetic happens in libpreworld_hip.so.  Names and argument order follow t
 reference operators these replace (cited per function, paths relative to the reference).
 """
 import ctypes
+import functools
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1451,3 +1453,108 @@ def occ_score(preds, gts, masks, n_cl, counts):
     _lib.call('pw_occ_score', P, G, M, H, n, int(n_cl), _chk(counts, _i64, 'counts'), _stream())
     del keep
     return counts
+
+
+OCC_FSCORE_MAX_H = 8
+OCC_FSCORE_MAX_Z = 64
+OCC_FSCORE_MAX_R = 7
+
+
+def fscore_offsets(threshold, voxel_size):
+    """The lattice form of occ_metrics.py:383-397's `distance < threshold`: an int8 table m of shape (2rx + 1, 2ry + 1), where a
+    voxel at integer offset (dx, dy, dz) from another lies closer than `threshold` (voxel centres, voxel_size = (vx, vy, vz))
+    exactly when |dz| <= m[dx + rx, dy + ry]; -1: no dz at that (dx, dy).  rx / ry are the largest |dx| / |dy| with an entry.
+    Distances are float64; |dz| is enumerated up to 63 (pw_occ_fscore's Z <= 64) and m is at most 63.  ValueError when some
+    lattice distance lies within 1e-9 (relative) of the threshold: there the reference's answer depends on how each point's
+    coordinates round, so no table reproduces it."""
+    t = float(threshold)
+    v = [float(x) for x in voxel_size]
+    if len(v) != 3 or not all(x > 0 for x in v) or not t > 0 or not np.isfinite(t):
+        raise ValueError('fscore_offsets: threshold and the three voxel sizes must be finite and > 0, got %r, %r'
+                         % (threshold, voxel_size))
+    r = [int(np.floor(t / x)) + 2 for x in v]
+    if max(r[:2]) > 64:
+        raise ValueError('fscore_offsets: threshold %r spans more than 63 columns of voxel size %r' % (threshold, voxel_size))
+    r[2] = min(r[2], 63)
+    dx, dy, dz = (np.arange(-k, k + 1, dtype=np.float64) * x for k, x in zip(r, v))
+    d = np.sqrt(dx[:, None, None] ** 2 + dy[None, :, None] ** 2 + dz[None, None, :] ** 2)
+    if np.any(np.abs(d - t) <= 1e-9 * t):
+        raise ValueError('fscore_offsets: a lattice distance of voxel size %r ties threshold %r (within 1e-9): the answer '
+                         'would depend on per-point rounding' % (tuple(voxel_size), threshold))
+    absz = np.abs(np.arange(-r[2], r[2] + 1))
+    m = np.where(d < t, absz[None, None, :], -1).max(axis=2)
+    used = m >= 0
+    rx = int(np.abs(np.arange(-r[0], r[0] + 1))[used.any(axis=1)].max())
+    ry = int(np.abs(np.arange(-r[1], r[1] + 1))[used.any(axis=0)].max())
+    return m[r[0] - rx:r[0] + rx + 1, r[1] - ry:r[1] + ry + 1].astype(np.int8)
+
+
+def _fscore_pad(m, rx, ry):
+    out = np.full((2 * rx + 1, 2 * ry + 1), -1, dtype=np.int8)
+    a, b = (m.shape[0] - 1) // 2, (m.shape[1] - 1) // 2
+    out[rx - a:rx + a + 1, ry - b:ry + b + 1] = m
+    return out
+
+
+@functools.lru_cache(maxsize=64)
+def _fscore_args(void, voxel_size, thr_acc, thr_cmpl):
+    """(void bitset, m_acc, m_cmpl, rx, ry) as ctypes arguments of pw_occ_fscore, both tables on one (rx, ry) window"""
+    if any(not 0 <= int(v) <= 255 for v in void):
+        raise ValueError('occ_fscore: void values must lie in [0, 255], got %r' % (void,))
+    bits = np.zeros(8, dtype=np.uint32)
+    for v in void:
+        bits[int(v) >> 5] |= np.uint32(1 << (int(v) & 31))
+    ma, mc = fscore_offsets(thr_acc, voxel_size), fscore_offsets(thr_cmpl, voxel_size)
+    rx = (max(ma.shape[0], mc.shape[0]) - 1) // 2
+    ry = (max(ma.shape[1], mc.shape[1]) - 1) // 2
+    ma, mc = _fscore_pad(ma, rx, ry).reshape(-1), _fscore_pad(mc, rx, ry).reshape(-1)
+    return ((ctypes.c_uint32 * 8)(*[int(b) for b in bits]), (ctypes.c_int8 * ma.size)(*[int(x) for x in ma]),
+            (ctypes.c_int8 * mc.size)(*[int(x) for x in mc]), rx, ry)
+
+
+def occ_fscore(preds, gts, masks, table, void=(17, 255), voxel_size=(0.4, 0.4, 0.4), thr_acc=0.6, thr_cmpl=0.6):
+    """table (H, 4) int64 += one sample's F-score counts {n_pred, n_pred_hit, n_gt, n_gt_hit} for H <= 8 horizons in ONE launch
+    (pw_occ_fscore; occ_metrics.py:322-410 Metric_FScore restated on the lattice, see fscore_offsets).  preds / gts: H contiguous
+    uint8 (X, Y, Z) device grids of one shape, Z <= 64; masks: None or H uint8 / bool device grids (an entry None: no mask;
+    where a mask is 0 pred and gt read as 255).  A voxel is occupied when its value is not in `void`.  Capturable: the pointers
+    and tables travel by value."""
+    H = len(preds)
+    if H < 1 or H > OCC_FSCORE_MAX_H or len(gts) != H or (masks is not None and len(masks) != H):
+        raise _lib.PreworldHipError('occ_fscore: 1 <= H <= %d horizons, one gt (and mask) per prediction' % OCC_FSCORE_MAX_H)
+    shape = tuple(preds[0].shape)
+    if len(shape) != 3 or any(tuple(t.shape) != shape for t in list(preds) + list(gts) + [m for m in (masks or ()) if m is not None]):
+        raise _lib.PreworldHipError('occ_fscore: every grid must be (X, Y, Z) of one shape, got %s'
+                                    % [tuple(t.shape) for t in preds])
+    if tuple(table.shape) != (H, 4):
+        raise _lib.PreworldHipError('occ_fscore: table must be (H, 4) = (%d, 4), got %s' % (H, tuple(table.shape)))
+    vb, ma, mc, rx, ry = _fscore_args(tuple(int(v) for v in void), tuple(float(v) for v in voxel_size), float(thr_acc),
+                                      float(thr_cmpl))
+    keep = [_chk(p, torch.uint8, 'pred') for p in preds] + [_chk(g, torch.uint8, 'gt') for g in gts]
+    P = (ctypes.c_void_p * H)(*[p.value for p in keep[:H]])
+    G = (ctypes.c_void_p * H)(*[g.value for g in keep[H:]])
+    M = None
+    if masks is not None:
+        ms = [None if m is None else _chk(m.view(torch.uint8) if m.dtype == torch.bool else m, torch.uint8, 'mask') for m in masks]
+        keep += [m for m in ms if m is not None]
+        M = (ctypes.c_void_p * H)(*[None if m is None else m.value for m in ms])
+    _lib.call('pw_occ_fscore', P, G, M, H, shape[0], shape[1], shape[2], vb, ma, mc, rx, ry, _chk(table, _i64, 'table'),
+              _stream())
+    del keep
+    return table
+
+
+def occ_fscore_accumulate(table, totals, empty):
+    """totals (H, 3) float64 += (accuracy, completeness, F1) of every sample of table ((H, 4) or (n_s, H, 4) int64, from
+    occ_fscore), in sample order, with occ_metrics.py:399-408's float64 arithmetic; empty (H,) int64 counts the samples with a
+    non-empty prediction and an empty ground truth (the reference raises there; they add (0, 0, 0)).  ONE launch
+    (pw_occ_fscore_accumulate), no host sync."""
+    t = table.reshape(-1, *table.shape[-2:]) if table.dim() >= 2 else table
+    if t.dim() != 3 or t.shape[-1] != 4:
+        raise _lib.PreworldHipError('occ_fscore_accumulate: table must be (H, 4) or (n_s, H, 4), got %s' % (tuple(table.shape),))
+    H = t.shape[1]
+    if tuple(totals.shape) != (H, 3) or tuple(empty.shape) != (H,):
+        raise _lib.PreworldHipError('occ_fscore_accumulate: totals (%d, 3) float64 and empty (%d,) int64, got %s and %s'
+                                    % (H, H, tuple(totals.shape), tuple(empty.shape)))
+    _lib.call('pw_occ_fscore_accumulate', _chk(t, _i64, 'table'), t.shape[0], H, _chk(totals, torch.float64, 'totals'),
+              _chk(empty, _i64, 'empty'), _stream())
+    return totals

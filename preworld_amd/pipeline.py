@@ -392,11 +392,15 @@ class StreamScheduler:
 class _ScoredCapture(CapturedSample):
     """CapturedSample whose graph also scores the sample: static GT / mask buffers (one row per scored horizon) and one
     pw_occ_score launch that zeroes, then fills the slot's per-sample table.  payload: the device rows of the host payload
-    (the OccHead's in-place `grids` rows when the layout allows, else a gather inside the graph), copied out by the stream."""
+    (the OccHead's in-place `grids` rows when the layout allows, else a gather inside the graph), copied out by the stream.
+    fscore: None, or dict(kernel=ops.occ_fscore keyword arguments, own_mask=bool): one more pw_occ_fscore launch into
+    `fs_table` over the same GT buffers -- and the mIoU mask buffers, or (own_mask) static mask buffers of its own."""
 
-    def __init__(self, net, frames, ego, n_steps, pred_keys=None, n_cl=18, masked=False, payload=False):
+    def __init__(self, net, frames, ego, n_steps, pred_keys=None, n_cl=18, masked=False, payload=False, fscore=None):
         self.pred_keys, self.n_cl, self.masked, self.want_payload = pred_keys, n_cl, masked, payload
+        self.fscore = fscore
         self.gt = self.mask = self.table = None
+        self.fs_table = self.fs_mask = None
         self.payload_dev = self.payload_keys = None
         super().__init__(net, frames, ego, n_steps=n_steps, d2h=False)
 
@@ -419,8 +423,16 @@ class _ScoredCapture(CapturedSample):
                 self.gt = torch.zeros((H,) + shape, dtype=torch.uint8, device=dev)
                 self.mask = torch.ones((H,) + shape, dtype=torch.uint8, device=dev) if self.masked else None
                 self.table = torch.zeros((H, ops.occ_score_bins(self.n_cl)), dtype=torch.int64, device=dev)
+                if self.fscore is not None:
+                    self.fs_table = torch.zeros((H, 4), dtype=torch.int64, device=dev)
+                    if self.fscore['own_mask']:
+                        self.fs_mask = torch.ones((H,) + shape, dtype=torch.uint8, device=dev)
             self.table.zero_()
             ops.occ_score(preds, list(self.gt), list(self.mask) if self.mask is not None else None, self.n_cl, self.table)
+            if self.fscore is not None:
+                fm = self.fs_mask if self.fscore['own_mask'] else (self.mask if self.fscore['mask_key'] is not None else None)
+                self.fs_table.zero_()
+                ops.occ_fscore(preds, list(self.gt), list(fm) if fm is not None else None, self.fs_table, **self.fscore['kernel'])
         return out
 
 
@@ -441,18 +453,22 @@ class _StreamSlot:
         if cap.payload_dev is not None:
             self.host = [torch.empty(tuple(cap.payload_dev.shape), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
             self.views = [{k: [h[i].numpy()] for i, k in enumerate(cap.payload_keys)} for h in self.host]
-        self.stage_gt = self.stage_mask = None
+        self.staging = {}                             # kind -> pinned (H, X, Y, Z) staging of host grids
         self._host_rows = ()
 
+    def _static(self, kind):
+        return {'gt': self.cap.gt, 'mask': self.cap.mask, 'fs_mask': self.cap.fs_mask}[kind]
+
     def _grids(self, sample):
-        """(kind, row, array) of the sample's GT (and mask) per scored horizon"""
+        """(kind, row, array) of the sample's GT (and masks) per scored horizon"""
         hz = self.owner.horizons
         out = [('gt', j, a) for j, a in enumerate(_grid_per_horizon(sample['gt'], hz))]
-        if self.cap.mask is not None:
-            m = sample.get(self.owner.mask_key)
-            if m is None:                             # no mask with this sample: every voxel counts (as add_batch with None)
-                m = np.ones(tuple(self.cap.mask.shape[1:]), dtype=np.uint8)
-            out += [('mask', j, a) for j, a in enumerate(_grid_per_horizon(m, hz))]
+        for kind, key in (('mask', self.owner.mask_key), ('fs_mask', self.owner.fs_mask_key)):
+            if self._static(kind) is not None:
+                m = sample.get(key)
+                if m is None:                         # no mask with this sample: every voxel counts (as add_batch with None)
+                    m = np.ones(tuple(self.cap.gt.shape[1:]), dtype=np.uint8)
+                out += [(kind, j, a) for j, a in enumerate(_grid_per_horizon(m, hz))]
         return out
 
     def stage(self, sample):
@@ -464,10 +480,9 @@ class _StreamSlot:
                     continue
                 if not rows:
                     self.staged.synchronize()
-                    if self.stage_gt is None:
-                        self.stage_gt = torch.empty(tuple(self.cap.gt.shape), dtype=torch.uint8, pin_memory=True)
-                        self.stage_mask = torch.empty(tuple(self.cap.gt.shape), dtype=torch.uint8, pin_memory=True)
-                dst = (self.stage_gt if kind == 'gt' else self.stage_mask)[j]
+                if kind not in self.staging:
+                    self.staging[kind] = torch.empty(tuple(self.cap.gt.shape), dtype=torch.uint8, pin_memory=True)
+                dst = self.staging[kind][j]
                 np.copyto(dst.numpy(), np.asarray(a).reshape(tuple(dst.shape)), casting='unsafe')
                 rows.append((kind, j))
         self._host_rows = tuple(rows)
@@ -483,7 +498,7 @@ class _StreamSlot:
         if cap.table is not None:
             for kind, j, a in self._grids(sample):
                 if isinstance(a, torch.Tensor) and a.is_cuda:
-                    dsts.append((cap.gt if kind == 'gt' else cap.mask)[j])
+                    dsts.append(self._static(kind)[j])
                     srcs.append(a.view(torch.uint8) if a.dtype == torch.bool else a)
         with torch.cuda.stream(st):
             # CapturedSample.run's guard: one pw_copy_many launch when every source qualifies, else one copy per tensor
@@ -494,7 +509,7 @@ class _StreamSlot:
                 for d, s_ in zip(dsts, srcs):
                     d.copy_(s_, non_blocking=True)
             for kind, j in self._host_rows:
-                (cap.gt if kind == 'gt' else cap.mask)[j].copy_((self.stage_gt if kind == 'gt' else self.stage_mask)[j], non_blocking=True)
+                self._static(kind)[j].copy_(self.staging[kind][j], non_blocking=True)
             if self._host_rows:
                 self.staged.record(st)
         self._host_rows = ()
@@ -524,7 +539,11 @@ class _StreamSlot:
                 self.owner.metric.add_counts(self.cap.table, 1, horizons=self.owner.horizons)
             else:
                 self.owner.metric.add_counts(self.cap.table, 1)
-        self.stream.wait_stream(ms)                   # the next replay re-zeroes the table: after the add
+            if self.cap.fs_table is not None:         # every horizon's F-score totals: one pw_occ_fscore_accumulate launch
+                ops.occ_fscore_accumulate(self.cap.fs_table, self.owner.fs_totals, self.owner.fs_empty)
+                for m in self.owner.fscore.values():
+                    m.cnt += 1
+        self.stream.wait_stream(ms)                   # the next replay re-zeroes the tables: after the adds
 
     def result(self, buf):
         return dict(self.views[buf]) if self.views is not None else {}
@@ -541,6 +560,10 @@ class SampleStream:
       (Metric_mIoU_Temporal for PreWorld4DTraj, Metric_mIoU with horizons (0,) for PreWorld) -- no per-sample result comes back to
       the host.  Samples then carry gt={h: (X,Y,Z) uint8} (or one grid) and mask_camera / mask_lidar (one grid or {h: grid}), numpy
       (through pinned staging) or device tensors.
+      score['fscore'] = dict(threshold_acc=0.6, threshold_complete=0.6, voxel_size=[0.4, 0.4, 0.4], range=..., void=[17, 255],
+      mask=None | 'camera' | 'lidar') (opt-in): one more launch in the graph, pw_occ_fscore over the same static GT buffers (and
+      the mIoU mask buffers when the masks agree; another mask gets static buffers of its own, filled from the samples' entry), and
+      every finished sample's counts are folded into `self.fscore` = {horizon: metrics.Metric_FScore} on the device.
 
     Every replay is range-checked before it counts (a miss: recalibrate, replay the same inputs, check again; still outside the
     window -> PreworldHipError).  Counters: `replays`, `recalibrations`, `recaptures`.
@@ -559,7 +582,9 @@ class SampleStream:
             raise ValueError('SampleStream: PreWorld4DTraj needs example ego states (B,1,21)')
         self.score = dict(score) if score is not None else None
         self.metric = None
-        self.horizons, self.mask_key, self.pred_keys = (), None, None
+        self.fscore = self.fs_totals = self.fs_empty = None
+        self.horizons, self.mask_key, self.pred_keys, self.fs_mask_key = (), None, None, None
+        self._fs_cap = None
         if self.score is not None:
             self.horizons = tuple(self.score.get('horizons', (0, 2, 4, 6) if self.temporal else (0,)))
             n_cl = self.score.setdefault('n_cl', 18)
@@ -578,6 +603,20 @@ class SampleStream:
                 dev = self.example[1].device
                 kw = dict(num_classes=n_cl, use_image_mask=mask == 'camera', use_lidar_mask=mask == 'lidar', device=dev)
                 self.metric = metrics.Metric_mIoU_Temporal(**kw) if self.temporal else metrics.Metric_mIoU(**kw)
+            fs = self.score.get('fscore')
+            if fs is not None:
+                fs = dict(fs)
+                fmask = fs.pop('mask', None)
+                if fmask not in ('camera', 'lidar', None):
+                    raise ValueError("SampleStream: fscore['mask'] must be 'camera', 'lidar' or None, got %r" % (fmask,))
+                fmask_key = {'camera': 'mask_camera', 'lidar': 'mask_lidar', None: None}[fmask]
+                group, self.fs_totals, self.fs_empty = metrics.Metric_FScore._group(
+                    len(self.horizons), use_image_mask=fmask == 'camera', use_lidar_mask=fmask == 'lidar',
+                    device=self.example[1].device, **fs)
+                self.fscore = dict(zip(self.horizons, group))
+                own = fmask_key is not None and fmask_key != self.mask_key
+                self.fs_mask_key = fmask_key if own else None
+                self._fs_cap = dict(kernel=group[0].kernel_args(), own_mask=own, mask_key=fmask_key)
         self.replays = self.recalibrations = self.recaptures = 0
         self.slots = []
         self.metric_stream = None
@@ -593,7 +632,7 @@ class SampleStream:
         self.close()
         frames, ego = self.example
         kw = dict(pred_keys=self.pred_keys, n_cl=self.score['n_cl'] if self.score else 18, masked=self.mask_key is not None,
-                  payload=self.payload)
+                  payload=self.payload, fscore=self._fs_cap)
         self.slots = [_StreamSlot(self, _ScoredCapture(self.net, frames, ego, self.n_steps, **kw)) for _ in range(self.in_flight)]
         self._fp = self._fingerprint()
 

@@ -1,6 +1,6 @@
 """Throughput of streaming evaluation (pipeline.SampleStream) at C3 against bench.py's raw captured loop, in one process.
 
-    python tools/bench_stream.py [--in-flight 2] [--samples 600] [--warmup 20] [--eval-samples 100]
+    python tools/bench_stream.py [--in-flight 2] [--samples 600] [--warmup 20] [--eval-samples 100] [--fscore]
 
 Prints one JSON line with samples/s for
   raw        bench.py's timed loop restated: M CapturedSamples (host payload in the graph, as bench.py's default), rotating
@@ -9,6 +9,11 @@ Prints one JSON line with samples/s for
   payload    SampleStream(payload=True, score=...): the same plus the 14-grid host payload per sample
   evaluate   harness.evaluate (eager, one sample at a time, host-side stacking) on the same samples
 raw, score and payload alternate (twice each, about 1.5 s per window at C3) so drift shows; the ratios use the means.
+--fscore measures instead, alternated three times each:
+  score      as above
+  fscore     the same stream with score['fscore'] (the camera mask): one more pw_occ_fscore launch in every graph and one
+             pw_occ_fscore_accumulate per sample
+and prints their ratio and the F-scores of the fscore stream.
 Inputs, GT grids and masks are resident in HBM (N_SETS distinct samples from fixed seeds); evaluate gets the GT as numpy, as
 its callers pass it."""
 import argparse
@@ -66,12 +71,38 @@ def time_stream(st, sets, n):
     return n / (time.perf_counter() - t0)
 
 
+def bench_fscore(net, sets, score, M, args):
+    """score-only stream against the same stream with the F-score, alternated"""
+    fs = dict(score, fscore=dict(threshold_acc=0.6, threshold_complete=0.6, voxel_size=[0.4, 0.4, 0.4], void=[17, 255],
+                                 mask='camera'))
+    st_b = SampleStream(net, sets[0]['frames'], sets[0]['ego'], in_flight=M, payload=False, score=score)
+    st_f = SampleStream(net, sets[0]['frames'], sets[0]['ego'], in_flight=M, payload=False, score=fs)
+    time_stream(st_b, sets, args.warmup)
+    time_stream(st_f, sets, args.warmup)
+    sc, sf = [], []
+    for _ in range(3):
+        sc.append(time_stream(st_b, sets, args.samples))
+        sf.append(time_stream(st_f, sets, args.samples))
+    b, f = float(np.mean(sc)), float(np.mean(sf))
+    res = dict(config='C3', in_flight=M, samples_timed=args.samples, score_samples_per_s=[round(v, 1) for v in sc],
+               fscore_samples_per_s=[round(v, 1) for v in sf], ratio_fscore_over_score=round(f / b, 4),
+               fscore={h: round(m.tot_f1_mean / m.cnt, 6) for h, m in st_f.fscore.items()},
+               fscore_cnt=st_f.fscore[HZ[0]].cnt, miou_cnt=st_f.metric.cnt,
+               counters={name: dict(replays=st.replays, recalibrations=st.recalibrations) for name, st in (('score', st_b),
+                                                                                                        ('fscore', st_f))},
+               gt_resident=True, torch=torch.__version__, pw_precision=os.environ.get('PW_PRECISION', 'h2'))
+    st_b.close()
+    st_f.close()
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--in-flight', type=int, default=2)
     ap.add_argument('--samples', type=int, default=600)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--eval-samples', type=int, default=100)
+    ap.add_argument('--fscore', action='store_true', help='score-only stream with and without the F-score (nothing else)')
     args = ap.parse_args()
     dev = 'cuda:0'
     M = max(1, args.in_flight)
@@ -79,6 +110,9 @@ def main():
     n_frames = 2
     sets = make_samples(dev, n_frames)
     score = dict(horizons=HZ, n_cl=18, mask='camera')
+    if args.fscore:
+        bench_fscore(net, sets, score, M, args)
+        return
 
     caps = [CapturedSample(net, *bench.make_inputs(dev, seed=k, n_frames=n_frames), n_steps=6, d2h=True) for k in range(M)]
     streams = [torch.cuda.Stream() for _ in range(M)]

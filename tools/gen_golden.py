@@ -814,6 +814,129 @@ def gen_metric(om):
          hist=m2.hist, iou=iu2, miou=np.float64(miou2))
 
 
+def _fscore_scene(rng, X=200, Y=200, Z=16):
+    """a structured occupancy scene: a ground slab of classes 11-16 under boxes of classes 1-10, the rest free (17); and a
+    prediction of it with boxes shifted by one or two voxels, dropped and invented, and noise voxels at exactly sqrt(2) and sqrt(3)
+    lattice units from ground-truth voxels (0.566 / 0.693 m at 0.4 m voxels: either side of the default 0.6 m)."""
+    gt = np.full((X, Y, Z), 17, np.uint8)
+    p = max(4, X // 10)
+    cls = rng.randint(11, 17, (-(-X // p), -(-Y // p)))
+    gt[:, :, 0] = np.kron(cls, np.ones((p, p), np.int64))[:X, :Y]
+    gt[:, :, 1] = np.where(rng.rand(X, Y) < 0.5, gt[:, :, 0], 17)
+    boxes = []
+    for _ in range(X * Y // 1000):
+        sx, sy, sz = rng.randint(2, 9), rng.randint(2, 9), rng.randint(1, max(2, Z // 3))
+        x0, y0, z0 = rng.randint(0, X - sx), rng.randint(0, Y - sy), rng.randint(1, 3)
+        c = rng.randint(1, 11)
+        gt[x0:x0 + sx, y0:y0 + sy, z0:z0 + sz] = c
+        boxes.append((x0, y0, z0, sx, sy, sz, c))
+    pred = gt.copy()
+    for (x0, y0, z0, sx, sy, sz, c) in boxes:
+        r = rng.rand()
+        if r < 0.4:                                            # shifted by one or two voxels along x, y or z
+            pred[x0:x0 + sx, y0:y0 + sy, z0:z0 + sz] = 17
+            d = [0, 0, 0]
+            d[rng.randint(0, 3)] = rng.choice([-2, -1, 1, 2])
+            xa, ya, za = max(0, x0 + d[0]), max(0, y0 + d[1]), max(0, z0 + d[2])
+            pred[xa:x0 + sx + d[0], ya:y0 + sy + d[1], za:z0 + sz + d[2]] = c
+        elif r < 0.55:                                         # dropped
+            pred[x0:x0 + sx, y0:y0 + sy, z0:z0 + sz] = 17
+    for _ in range(len(boxes) // 3):                           # invented
+        sx, sy, sz = rng.randint(2, 6), rng.randint(2, 6), rng.randint(1, 3)
+        x0, y0, z0 = rng.randint(0, X - sx), rng.randint(0, Y - sy), rng.randint(2, Z - sz)
+        pred[x0:x0 + sx, y0:y0 + sy, z0:z0 + sz] = rng.randint(1, 11)
+    occ = np.argwhere((gt != 17) & (gt != 255))
+    for dist2 in (2, 3):                                       # noise at sqrt(2) / sqrt(3) lattice units from a gt voxel
+        pick = occ[rng.randint(0, len(occ), X * Y // 6)]
+        offs = np.array([o for o in np.ndindex(3, 3, 3) if sum((np.array(o) - 1) ** 2) == dist2]) - 1
+        q = pick + offs[rng.randint(0, len(offs), len(pick))]
+        q = q[np.all((q >= 0) & (q < (X, Y, Z)), axis=1)]
+        q = q[gt[q[:, 0], q[:, 1], q[:, 2]] == 17]
+        # keep only noise whose nearest gt voxel is exactly that far: no gt voxel at a smaller lattice distance
+        ok = np.ones(len(q), bool)
+        for o in np.ndindex(3, 3, 3):
+            o = np.array(o) - 1
+            if 0 < (o ** 2).sum() < dist2:
+                r_ = q + o
+                inb = np.all((r_ >= 0) & (r_ < (X, Y, Z)), axis=1)
+                g_ = np.full(len(q), 17)
+                g_[inb] = gt[r_[inb, 0], r_[inb, 1], r_[inb, 2]]
+                ok &= (g_ == 17) | (g_ == 255)
+        q = q[ok]
+        pred[q[:, 0], q[:, 1], q[:, 2]] = rng.randint(1, 17, len(q))
+    return pred, gt
+
+
+def _fscore_masks(rng, X, Y, Z):
+    """camera mask: a field of view (a wedge in x / y) with per-voxel dropout; lidar mask: a range ring with dropout"""
+    xs, ys = np.meshgrid(np.arange(X) - X / 2 + 0.5, np.arange(Y) - Y / 2 + 0.5, indexing='ij')
+    cam = (np.abs(np.arctan2(ys, xs)) < 2.2)[:, :, None] & (rng.rand(X, Y, Z) < 0.9)
+    rr = np.hypot(xs, ys)
+    lid = ((rr > X * 0.05) & (rr < X * 0.45))[:, :, None] & (rng.rand(X, Y, Z) < 0.85)
+    return cam, lid
+
+
+def gen_fscore(om):
+    """Metric_FScore (occ_metrics.py:322-410, the imported reference with its sklearn KDTrees) on structured scenes.  Per case:
+    the grids, every sample's (acc, cmpl, f) -- the tot_* of a fresh reference metric per sample, i.e. tot_* minus 0 -- and the
+    totals of one reference metric over the case's samples in order.  The reference writes 255 into its inputs under a mask:
+    it gets copies."""
+    import contextlib
+    import io
+    rng = np.random.RandomState(61)
+    cases = []                                                 # (name, metric kwargs, samples [(pred, gt, mask_lidar, mask_camera)])
+
+    def scenes(n, X=200, Y=200, Z=16):
+        out = []
+        for _ in range(n):
+            pred, gt = _fscore_scene(rng, X, Y, Z)
+            cam, lid = _fscore_masks(rng, X, Y, Z)
+            out.append((pred, gt, lid, cam))
+        return out
+    cases.append(('plain', dict(), scenes(2)))
+    cases.append(('camera', dict(use_image_mask=True), scenes(2)))
+    cases.append(('lidar', dict(use_lidar_mask=True), scenes(1)))
+    cases.append(('camera_void17', dict(use_image_mask=True, void=[17]), scenes(1)))
+    cases.append(('thr', dict(threshold_acc=1.0, threshold_complete=0.45), scenes(1)))
+    cases.append(('voxel', dict(voxel_size=[0.5, 0.5, 0.25]), scenes(1)))
+    s = scenes(1)[0]
+    gt = s[1].copy()
+    gt[:60, :, 4:] = np.where(gt[:60, :, 4:] == 17, 255, gt[:60, :, 4:])     # unobserved space
+    gt[150:, 150:, :] = 255
+    cases.append(('gt255', dict(), [(s[0], gt, s[2], s[3])]))
+    s = scenes(1)[0]
+    cases.append(('allfree', dict(), [(np.full_like(s[0], 17), s[1], s[2], s[3])]))
+    cases.append(('small', dict(use_image_mask=True), scenes(2, 100, 100, 8)))
+    out = {'cases': np.array([c[0] for c in cases])}
+    for name, kw, samples in cases:
+        ref = om.Metric_FScore(**kw)
+        per = []
+        for pred, gt, lid, cam in samples:
+            one = om.Metric_FScore(**kw)
+            one.add_batch(pred.copy(), gt.copy(), lid.copy(), cam.copy())
+            ref.add_batch(pred.copy(), gt.copy(), lid.copy(), cam.copy())
+            per.append((one.tot_acc - 0.0, one.tot_cmpl - 0.0, one.tot_f1_mean - 0.0))
+        with contextlib.redirect_stdout(io.StringIO()):
+            ref.count_fscore()
+        full = om.Metric_FScore(**kw)
+        pre = name + '_'
+        out[pre + 'pred'] = np.stack([t[0] for t in samples])
+        out[pre + 'gt'] = np.stack([t[1] for t in samples])
+        if full.use_lidar_mask:
+            out[pre + 'mask_lidar'] = np.stack([t[2] for t in samples])
+        if full.use_image_mask:
+            out[pre + 'mask_camera'] = np.stack([t[3] for t in samples])
+        out[pre + 'per_sample'] = np.array(per, np.float64)
+        out[pre + 'totals'] = np.array([ref.tot_acc, ref.tot_cmpl, ref.tot_f1_mean], np.float64)
+        out[pre + 'cnt'] = np.int64(ref.cnt)
+        out[pre + 'thresholds'] = np.array([full.threshold_acc, full.threshold_complete], np.float64)
+        out[pre + 'voxel_size'] = np.array(full.voxel_size, np.float64)
+        out[pre + 'void'] = np.array(full.void, np.int64)
+        out[pre + 'masks'] = np.array([full.use_lidar_mask, full.use_image_mask])
+        print('fscore %-14s %s  per-sample %s' % (name, out[pre + 'totals'], out[pre + 'per_sample'].tolist()))
+    save('fscore.npz', **out)
+
+
 # ----------------------------------------------------------------------------- configs -> resolved model dicts
 def _merge_cfg(a, b):
     """mmcv Config._merge_a_into_b: child `a` over base `b`, dicts merged recursively unless a['_delete_']."""
@@ -1401,6 +1524,8 @@ def main():
         gen_e2e_pretrain(vtm, occ, nh)
     if want('e2e_train_b2'):
         gen_e2e_train_b2(vtm, occ)
+    if want('fscore'):
+        gen_fscore(om)
     if only:
         return
     gen_kat(bp)
