@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: samples/s of PreWorld's camera->voxel occupancy hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C2] [--mode replicas|sharded] [--no-graph] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C2|C5] [--mode replicas|sharded] [--no-graph] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -24,13 +24,16 @@ synthetic -- there is no dataset or checkpoint in this environment.
   job -- frames lifted on different ranks + RCCL all_gather of the voxel features, encoder on every rank, the 7 states
   forecast + decoded round-robin + RCCL all_gather of the uint8 grids (harness.simple_test_sharded) -> strong scaling.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline line; every figure that needs runs
+of its own is measured only with --full, and then the JSON line also carries
   roofline     -- the kernel with the largest share of the step BY ROCPROF KERNEL NAME (plus the HBM-bound voxel-pooling
                   kernel under `also`): algorithmic work / HIP-event duration measured live on the launch stream
   cpu_baseline -- the same C3 sample at FULL size on the host cores (no extrapolation): the PyTorch-CPU composition
                   (median of 5 after a warm-up) and the OpenMP port (the reference has no CPU path for its native ops).
   extra        -- measured after the timed region: c2 (single frame, 1 state), c5 (render head forward / forward + backward, the
                   pre-train step), train (the voxel-side fine-tune step, forward + backward); --no-extra skips them.
+and config.single_sample_latency_ms, config.replay_same_inputs, config.sharded_phase_ms_rank0 (--mode sharded); with --config C5,
+the forward-only, bf16-grid, transparent-scene, 38 400 x 417 and pre-train figures and the roofline.  Without --full these are null.
 
 --dump-outputs DIR writes the result of the last timed step (rank 0's) as DIR/<name>.npy (float32; arrays above 2^20 elements as a
 seeded sample of 2^19; at most 64 MB in all) and lists them under `dump_outputs`: the same arguments give the same inputs on every
@@ -415,7 +418,8 @@ def c5_result(args, quick=False):
                     the fraction that does is measured on the device and reported (`terminated_frac`);
       'transparent' density 4.0 in a ground slab and a ring of blocks, -8 elsewhere: alpha ~3e-5 per sample, NO ray terminates
                     (every round-2..4 figure was of this kind).
-    `value` = rays/s of forward + backward on the mixed scene; the reference's own 38 400 x 417 shape is in config for both."""
+    `value` = rays/s of forward + backward on the mixed scene; the reference's own 38 400 x 417 shape is in config for both.
+    Without --full only that headline is measured: the transparent scene, the other figures and the roofline are null."""
     from preworld_amd import modules as M
     dev = 'cuda:0'
     T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)                                   # noqa: E731
@@ -476,20 +480,23 @@ def c5_result(args, quick=False):
         t_fb, out = timed(fwd_bwd, steps, args.warmup)
         if name == 'mixed':
             last.update(out)
+        fb = dict(st, fwd_bwd_ms=round(t_fb * 1e3, 4), rays_per_s_fwd_bwd=round(3072 / t_fb, 1),
+                  fwd_bwd_samples_per_s=round(3072 * 96 / t_fb, 0))
+        if not args.full:
+            return fb, None
         t_f, t_f16 = timed(fwd, steps, args.warmup)[0], timed(fwd16, steps, args.warmup)[0]
         rf, rfb, _, st_ref = shape(38400, head.t_table(dev))
         t_rf, t_rfb = timed(rf, 10, 2)[0], timed(rfb, 5, 1)[0]
-        return dict(st, forward_ms=round(t_f * 1e3, 4), forward_bf16_grid_ms=round(t_f16 * 1e3, 4), fwd_bwd_ms=round(t_fb * 1e3, 4),
-                    rays_per_s_fwd_bwd=round(3072 / t_fb, 1), forward_samples_per_s=round(3072 * 96 / t_f, 0),
-                    fwd_bwd_samples_per_s=round(3072 * 96 / t_fb, 0),
+        return dict(fb, forward_ms=round(t_f * 1e3, 4), forward_bf16_grid_ms=round(t_f16 * 1e3, 4),
+                    forward_samples_per_s=round(3072 * 96 / t_f, 0),
                     reference_shape_38400x417=dict(st_ref, forward_ms=round(t_rf * 1e3, 3), fwd_bwd_ms=round(t_rfb * 1e3, 3),
-                                                   forward_samples_per_s=round(38400 * 417 / t_rf, 0))), grid.numel() * 4, t_f
-    mixed, grid_bytes, t_f = scene('mixed')
+                                                   forward_samples_per_s=round(38400 * 417 / t_rf, 0))), grid.numel() * 4 / t_f
+    mixed, fwd_bytes_per_s = scene('mixed')
     dumped = dump_outputs(last, args.dump_outputs) if args.dump_outputs and not quick else None
     last.clear()
-    transparent, _, _ = scene('transparent')
-    pretrain = pretrain_step_ms(dev, args)
-    traffic, traffic_src = _pmc_traffic('k_render_rays')
+    transparent = scene('transparent')[0] if args.full else None
+    pretrain = pretrain_step_ms(dev, args) if args.full else None
+    traffic, traffic_src = _pmc_traffic('k_render_rays') if args.full else (None, None)
     res = {
         'metric': 'rays/sec (render head forward + backward, 6 cams x 512 rays x 96 samples)', 'value': mixed['rays_per_s_fwd_bwd'],
         'unit': 'rays/s', 'n_gpus': 1, 'steps': steps, 'warmup': args.warmup, 'ms_per_step': mixed['fwd_bwd_ms'],
@@ -499,16 +506,16 @@ def c5_result(args, quick=False):
                         '(%.0f %% of the rays terminate at T < 1e-3); a step = forward + zero-fill of the gradient grid + backward'
                         % (100 * mixed['terminated_frac']),
             'terminated_frac': mixed['terminated_frac'], 'mixed': mixed, 'transparent': transparent,
-            'forward_ms': mixed['forward_ms'], 'reference_shape_38400x417': mixed['reference_shape_38400x417'],
+            'forward_ms': mixed.get('forward_ms'), 'reference_shape_38400x417': mixed.get('reference_shape_38400x417'),
             'pretrain_step': pretrain,
             'backward': 'pw_render_rays_backward_sorted: entries sorted by voxel, 64-bit fixed-point segmented sums, no float atomics, '
                         'bit-reproducible',
             'note': 'extra, non-headline entry; the headline metric is --config C3'},
-        'roofline': {'bound': 'hbm', 'kernel': 'k_render_rays', 'achieved': round(grid_bytes / t_f / 1e9, 1), 'peak': PEAK_HBM_GBPS,
-                     'unit': 'GB/s', 'frac': round(grid_bytes / t_f / 1e9 / PEAK_HBM_GBPS, 4), 'traffic': traffic,
+        'roofline': {'bound': 'hbm', 'kernel': 'k_render_rays', 'achieved': round(fwd_bytes_per_s / 1e9, 1), 'peak': PEAK_HBM_GBPS,
+                     'unit': 'GB/s', 'frac': round(fwd_bytes_per_s / 1e9 / PEAK_HBM_GBPS, 4), 'traffic': traffic,
                      'traffic_unit': 'HBM bytes per forward launch at 3072 x 96 (PMC, %s)' % traffic_src if traffic_src else None,
                      'note': 'algorithmic bytes = the 61 MB packed grid read once per forward (SURVEY 8d); the kernel is bound by the '
-                             'per-ray scan and gather latency, not by HBM (profiles/r02_render_c5.txt)'},
+                             'per-ray scan and gather latency, not by HBM (profiles/r02_render_c5.txt)'} if args.full else None,
     }
     if dumped is not None:
         res['dump_outputs'] = dict(dir=args.dump_outputs, arrays=dumped)
@@ -608,8 +615,8 @@ def extra_figures(args, dev):
     except Exception as e:                                                # noqa: BLE001
         ex['train'] = {'error': repr(e)[:300]}
     torch.cuda.empty_cache()
-    ex['f32_exact'] = _sub_json([sys.executable, os.path.abspath(__file__), '--steps', '10', '--warmup', '3', '--settle-s', '1', '--no-extra',
-                                 '--no-cpu-baseline'], dict(PW_PRECISION='f32'),
+    ex['f32_exact'] = _sub_json([sys.executable, os.path.abspath(__file__), '--steps', '10', '--warmup', '3', '--settle-s', '1', '--full',
+                                 '--no-extra', '--no-cpu-baseline'], dict(PW_PRECISION='f32'),
                                 lambda r: dict(workload='C3 under PW_PRECISION=f32: every product an exact-fp32 MFMA (Winograd / direct conv '
                                                         'kernels, k_occ_head_wino, k_forecast), same captured step, same rotating inputs',
                                                samples_per_s=r['value'], ms_per_step=r['ms_per_step'], steps=r['steps'], dtype=r['dtype'],
@@ -620,7 +627,7 @@ def extra_figures(args, dev):
                                                              'roofline_executed_frac = FLOPs the matrix pipe executes / peak'))
     # BASELINE configs[3] at world 1 (its own process: it initialises a 1-rank RCCL group): pipeline.ShardedSample, three graphs per rank
     ex['sharded_w1'] = _sub_json([sys.executable, os.path.abspath(__file__), '--mode', 'sharded', '--steps', '30', '--warmup', '5', '--settle-s', '1',
-                                  '--no-extra', '--no-cpu-baseline'], dict(MASTER_PORT=str(29600 + os.getpid() % 300)),
+                                  '--full', '--no-extra', '--no-cpu-baseline'], dict(MASTER_PORT=str(29600 + os.getpid() % 300)),
                                  lambda r: dict(workload='C3 sample in the sharded latency mode (frames / states owned round-robin, two collectives), '
                                                          'world 1: every phase on this GPU, collectives trivial', samples_per_s=r['value'],
                                                 ms_per_step=r['ms_per_step'], steps=r['steps'], phase_ms_rank0=r['config']['sharded_phase_ms_rank0'],
@@ -795,8 +802,12 @@ def main():
     ap.add_argument('--mode', default='replicas', choices=['replicas', 'sharded'])
     ap.add_argument('--no-graph', action='store_true', help='eager launches instead of hipGraph replay')
     ap.add_argument('--no-d2h', action='store_true', help='leave the occupancy grids on the device (no host payload)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extra', action='store_true', help='skip the compact C2 / C5 figures appended after the timed region')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: roofline, sustained MFMA rate, latency, same-input replay, '
+                         'sharded phase times, the extra figures and the CPU baseline (C5: the forward, bf16, transparent, '
+                         'reference-shape and pre-train figures)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extra', action='store_true', help='with --full: skip the compact C2 / C5 figures appended after the timed region')
     ap.add_argument('--dump-outputs', metavar='DIR',
                     help='after the timed steps, write what the last one computed to DIR/<name>.npy (rank 0; see dump_outputs)')
     args = ap.parse_args()
@@ -883,7 +894,7 @@ def main():
 
     # live per-kernel timing for the roofline object (eager, HIP events on the launch stream)
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         n_probe = 3
         # one stream for this pass: with the adjacent frame's lift forked onto a side stream the events around a launch
         # would also span whatever the other branch is running
@@ -947,7 +958,7 @@ def main():
     while time.perf_counter() < t_settle:
         run_steps(M)
         torch.cuda.synchronize()
-    if graph is not None and M > 1 and rank == 0:        # single-sample latency, reported next to the throughput
+    if graph is not None and M > 1 and rank == 0 and args.full:        # single-sample latency, beside the throughput
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(20):
@@ -979,7 +990,7 @@ def main():
     if graph is not None:
         bad = [c.bad_replays() for c in caps]                    # (replays outside their calibrated ranges, replays audited) per captured step
         audit = dict(replays_audited=int(sum(b[1] for b in bad)), recalibrations=int(sum(b[0] for b in bad)))
-        if rank == 0 and world == 1:
+        if rank == 0 and world == 1 and args.full:
             # the round-3 figure beside it: the same captured steps replayed on their own calibration samples, no input copies
             run_steps(args.warmup, rotate=False)
             torch.cuda.synchronize()
@@ -1003,7 +1014,7 @@ def main():
                 '0.5 s on this box right after the timed region; frac_of_it = executed_tflops / tflops '
                 '(profiles/r03_power_wall.txt: with real data the socket sits at its power cap and the clock follows)')
 
-    if sharded:
+    if sharded and args.full:
         # per-phase times of this mode (HIP events, a few passes AFTER the timed region; rank 0's own phases), so that a multi-GPU
         # run explains itself: which part is divided by N, which is not, what the two all_gathers cost
         acc = {}
@@ -1099,9 +1110,9 @@ def main():
         }
         if dumped is not None:
             res['dump_outputs'] = dict(dir=args.dump_outputs, arrays=dumped)
-        if world == 1 and not sharded and args.config == 'C3' and not args.no_extra:
+        if args.full and world == 1 and not sharded and args.config == 'C3' and not args.no_extra:
             res['extra'] = extra_figures(args, dev)
-        if not args.no_cpu_baseline and world == 1 and not sharded:
+        if args.full and not args.no_cpu_baseline and world == 1 and not sharded:
             res['cpu_baseline'] = cpu_baseline(sd, step_gflop=(roofline or {}).get('step_gflop'))
         print(json.dumps(res))
     if dist is not None:

@@ -207,6 +207,27 @@ def test_two_samples_in_flight_do_not_interfere():
             assert torch.equal(c.out[k][0], v), k
 
 
+def test_bench_py_plain_run_measures_the_headline_only():
+    """a plain `bench.py --gpus 1 --steps K --warmup W` times the K captured steps and prints ONE JSON line with the headline; the
+    figures that need runs of their own (roofline, latency, same-input replay, extra, cpu_baseline) come only with --full."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '1', '--settle-s', '0.1']
+    out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, out.stdout[-2000:]
+    r = json.loads(lines[0])
+    assert r['unit'] == 'samples/s' and r['higher_is_better'] is True and r['n_gpus'] == 1 and r['steps'] == 4 and r['warmup'] == 1
+    assert abs(r['value'] - 4 / (r['ms_per_step'] * 4e-3)) < 1e-2 * r['value']
+    assert r['config']['replays_audited'] >= 5 and r['config']['states_per_sample'] == 7
+    assert r['roofline'] is None and 'extra' not in r and 'cpu_baseline' not in r
+    assert r['config']['single_sample_latency_ms'] is None and r['config']['replay_same_inputs'] is None
+
+
 def test_pretrain_attribute_decode_branch_matches_oracle():
     """if_post_finetune=False (preworld_temporal_traj.py:224-301): density-threshold + semantic-MLP decode of
     the 7 states, named 0s, 2s..7s like the reference, against the oracle's attribute decode.  The synthetic
