@@ -3,6 +3,11 @@ path -- build the detector from a restated config dict, load a state dict by the
 names, feed lifted inputs, collect `semantic_occ_{k}s`, stack states 0/2/4/6
 (mmdet3d/apis/test.py:218-223) and score them with Metric_mIoU_Temporal
 (mmdet3d/datasets/occ_metrics.py:413-594).  GPU only: every op goes through libpreworld_hip.so."""
+import collections
+import collections.abc
+import os
+import time
+
 import numpy as np
 import torch
 
@@ -188,37 +193,196 @@ def simple_test_sharded(net, frames, ego, n_steps=6, group=None, gather_on_host=
 
 
 @torch.no_grad()
-def evaluate_stream(net, samples, in_flight=2, use_image_mask=True, keep_stacks=False, fscore=None):
+def evaluate_stream(net, samples, in_flight=2, use_image_mask=True, keep_stacks=False, fscore=None, distributed=False, group=None,
+                    dump_dir=None, stats=None):
     """harness.evaluate through pipeline.SampleStream: `in_flight` captured samples on their own HIP streams, every replay
     range-checked, each sample scored on the device by one pw_occ_score launch inside its graph (no per-sample D2H copy).
     samples: a list or iterable of the same dicts as evaluate (the first one fixes the shapes the graphs are captured for).
     Returns what evaluate returns: (report, stacks or None, metric) -- stacks (the {0,2,4,6} stack per sample, numpy) only when
     keep_stacks=True, which turns the payload copy on.
     fscore: as for evaluate -- one more launch inside each sample's graph (pw_occ_fscore) and one fold per finished sample
-    (pw_occ_fscore_accumulate); then report['fscore'] = {idx: tot_f1_mean / cnt} and metric.fscore = {idx: Metric_FScore}."""
+    (pw_occ_fscore_accumulate); then report['fscore'] = {idx: tot_f1_mean / cnt} and metric.fscore = {idx: Metric_FScore}.
+    dump_dir: the reference's --dump_dir (apis/test.py:225-232): each sample's stack is written to
+    <dump_dir>/<scene_name>/<sample_idx>.npy as np.save(path, [stack]) -- a (1, 4, X, Y, Z) uint8 array -- with scene_name and
+    sample_idx read from the sample dict (ValueError without them).  Turns the payload copy on.
+    distributed=True: evaluate one split across the ranks of an initialised torch.distributed group (`group`, or the default
+    group), one process per GPU; see _evaluate_stream_distributed.  Every rank returns the whole split's (report, None, metric).
+    stats (dict): receives this process's 'samples', 'replays', 'recalibrations', 'recaptures' and the seconds of 'capture_s'
+    (the slots' capture), 'stream_s' (first sample enqueued to the stream drained) and 'reduce_s' (drained to the final report)."""
+    if distributed:
+        return _evaluate_stream_distributed(net, samples, in_flight, use_image_mask, keep_stacks, fscore, group, dump_dir, stats)
     from .pipeline import SampleStream
     it = iter(samples)
     first = next(it, None)
     if first is None:
         raise ValueError('evaluate_stream: no samples')
+    if dump_dir is not None:
+        _dump_path(dump_dir, first)
     horizons = (0, 2, 4, 6)
     score = dict(horizons=horizons, n_cl=18, mask='camera' if use_image_mask else None)
     if fscore is not None:
         score['fscore'] = dict(fscore)
-    stream = SampleStream(net, first['frames'], first['ego'], in_flight=in_flight, n_steps=6, payload=keep_stacks, score=score)
+    t0 = time.perf_counter()
+    stream = SampleStream(net, first['frames'], first['ego'], in_flight=in_flight, n_steps=6,
+                          payload=keep_stacks or dump_dir is not None, score=score)
+    t1 = time.perf_counter()
     stacks = [] if keep_stacks else None
     try:
-        for res in stream.run(_chain(first, it)):
-            if keep_stacks:
-                stacks.append(np.stack([res['semantic_occ_%ds' % h][0] for h in horizons], axis=0))
-        torch.cuda.current_stream().synchronize()
+        n = _drain(stream, _chain(first, it), False, horizons, stacks, dump_dir)
     finally:
         stream.close()
+    t2 = time.perf_counter()
     report = stream.metric.report()
     if fscore is not None:
         stream.metric.fscore = stream.fscore
         report['fscore'] = {h: f.tot_f1_mean / f.cnt for h, f in stream.fscore.items()}
+    if stats is not None:
+        stats.update(samples=n, replays=stream.replays, recalibrations=stream.recalibrations, recaptures=stream.recaptures,
+                     capture_s=t1 - t0, stream_s=t2 - t1, reduce_s=time.perf_counter() - t2)
     return report, stacks, stream.metric
+
+
+def _dump_path(dump_dir, sample):
+    """<dump_dir>/<scene_name>/<sample_idx>.npy (apis/test.py:226-232)"""
+    if 'scene_name' not in sample or 'sample_idx' not in sample:
+        raise ValueError('evaluate_stream: dump_dir needs scene_name and sample_idx in every sample')
+    return os.path.join(dump_dir, str(sample['scene_name']), '%s.npy' % (sample['sample_idx'],))
+
+
+def _drain(stream, items, indexed, horizons, stacks, dump_dir):
+    """run the stream over `items` to the end; stacks (a list) receives every stack, dump_dir every file.  Returns the count."""
+    paths = collections.deque()
+
+    def feed():
+        for item in items:
+            if dump_dir is not None:
+                paths.append(_dump_path(dump_dir, item[1] if indexed else item))
+            yield item
+    n = 0
+    for res in stream.run(feed(), indexed=indexed):
+        n += 1
+        if stacks is not None or dump_dir is not None:
+            st = np.stack([res['semantic_occ_%ds' % h][0] for h in horizons], axis=0)
+            if stacks is not None:
+                stacks.append(st)
+            if dump_dir is not None:
+                path = paths.popleft()
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+                np.save(path, [st])
+    torch.cuda.current_stream().synchronize()
+    return n
+
+
+def _is_sequence(samples):
+    return hasattr(samples, '__len__') and hasattr(samples, '__getitem__') and not isinstance(samples, collections.abc.Mapping)
+
+
+def _evaluate_stream_distributed(net, samples, in_flight, use_image_mask, keep_stacks, fscore, group, dump_dir, stats):
+    """evaluate_stream(distributed=True): what tools/dist_test_temporal.sh -> multi_gpu_test_temporal -> dataset.evaluate does
+    (apis/test.py:198-256, nuscenes_dataset_occ_trajectory.py:478-526), without moving a prediction between processes.
+
+    * Rank r of W evaluates the global samples i with i % W == r (parallel.eval_shard: DistributedSampler(shuffle=False) without
+      its padding).  samples: a sequence (len + indexing; a rank reads its own items and item 0 only) or an iterable (every rank
+      walks ALL of it and skips the other ranks' items: its items should be cheap handles, e.g. loading their tensors lazily).
+    * Every rank captures its slots on global sample 0, so sample i replays under the activation ranges the single-process stream
+      uses; a range miss still recalibrates that rank's slot locally.  A rank with no sample (W > N) captures nothing.
+    * Once the rank's stream has drained: parallel.all_agree on "finished without error" (any failure -> PreworldHipError on
+      EVERY rank, chained to the local error where there is one), then parallel.reduce_eval_counts: SUM of every horizon's
+      confusion matrix and binary histogram and the counts.  With fscore, sample i's (H, 4) counts were written to row i of an
+      (n, H, 4) int64 table during the stream (nothing folded); N, the split's size, is a MAX all-reduce of the rows each rank
+      has seen (len(samples), or the items walked), the tables are SUM-reduced and ONE pw_occ_fscore_accumulate folds all N
+      rows in index order -- the single-process stream's input order, so the float64 totals and n_empty_gt are identical.
+      The same collectives run on every rank whatever its sample count.  RCCL ('nccl') reduces device tensors; any other
+      backend (gloo) gets them through host memory.
+    keep_stacks raises ValueError (predictions stay where they were made: use dump_dir, each rank writes its own samples)."""
+    import torch.distributed as dist
+    from . import ops, parallel
+    from .pipeline import SampleStream
+    if keep_stacks:
+        raise ValueError('evaluate_stream(distributed=True): predictions stay on the rank that made them -- use dump_dir')
+    if not (dist.is_available() and dist.is_initialized()):
+        raise ValueError('evaluate_stream(distributed=True) needs an initialised torch.distributed process group')
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    via_host = dist.get_backend(group) != 'nccl'
+    seen = [0]
+    if _is_sequence(samples):
+        seen[0] = len(samples)
+        if not seen[0]:
+            raise ValueError('evaluate_stream: no samples')
+        first = samples[0]
+        own = ((i, samples[i]) for i in parallel.eval_shard(seen[0], rank, world))
+    else:
+        it = iter(samples)
+        first = next(it, None)
+        if first is None:
+            raise ValueError('evaluate_stream: no samples')
+
+        def walk():
+            seen[0] = 1
+            if rank == 0:
+                yield 0, first
+            for i, s in enumerate(it, 1):
+                seen[0] = i + 1
+                if i % world == rank:
+                    yield i, s
+        own = walk()
+    if dump_dir is not None:
+        _dump_path(dump_dir, first)
+    horizons = (0, 2, 4, 6)
+    dev = first['ego'].device
+    score = dict(horizons=horizons, n_cl=18, mask='camera' if use_image_mask else None)
+    if fscore is not None:
+        score['fscore'] = dict(fscore)
+    stream, err, n = None, None, 0
+    t0 = t1 = time.perf_counter()
+    try:
+        head = next(own, None)
+        if head is not None:
+            stream = SampleStream(net, first['frames'], first['ego'], in_flight=in_flight, n_steps=6,
+                                  payload=dump_dir is not None, score=score)
+            t1 = time.perf_counter()
+            n = _drain(stream, _chain(head, own), True, horizons, None, dump_dir)
+    except Exception as e:                  # every rank must still reach the agreement below
+        err = e
+    t2 = time.perf_counter()
+    try:
+        if not parallel.all_agree(err is None, dev, group, via_host):
+            raise ops._lib.PreworldHipError('evaluate_stream(distributed=True): rank %d of %d: %s' % (
+                rank, world, 'failed: %r' % (err,) if err is not None else 'another rank failed')) from err
+        if stream is not None:
+            metric, fs, totals, empty, rows = stream.metric, stream.fscore, stream.fs_totals, stream.fs_empty, stream.fs_rows
+        else:
+            metric = metrics.Metric_mIoU_Temporal(num_classes=18, use_image_mask=use_image_mask, device=dev)
+            fs = totals = empty = rows = None
+            if fscore is not None:
+                kw = dict(fscore)
+                fmask = kw.pop('mask', None)
+                group_fs, totals, empty = metrics.Metric_FScore._group(
+                    len(horizons), use_image_mask=fmask == 'camera', use_lidar_mask=fmask == 'lidar', device=dev, **kw)
+                fs = dict(zip(horizons, group_fs))
+        if fs is not None and rows is None:
+            rows = torch.zeros((0, len(horizons), 4), dtype=torch.int64, device=dev)
+        mine = [n] + ([stream.replays, stream.recalibrations, stream.recaptures] if stream is not None else [0, 0, 0])
+        summed, rows = parallel.reduce_eval_counts(metric, rows if fs is not None else None, seen[0], mine, group, via_host)
+        N = seen[0] if rows is None else rows.shape[0]
+        if summed[0] != N or metric.cnt != N:
+            raise ops._lib.PreworldHipError('evaluate_stream(distributed=True): %d samples scored across the ranks for a split of %d'
+                                            % (summed[0], N))
+        report = metric.report()
+        if fs is not None:
+            ops.occ_fscore_accumulate(rows, totals, empty)         # all N rows in index order: the single-process fold
+            for m in fs.values():
+                m.cnt = N
+            metric.fscore = fs
+            report['fscore'] = {h: f.tot_f1_mean / f.cnt for h, f in fs.items()}
+    finally:
+        if stream is not None:
+            stream.close()
+    if stats is not None:
+        stats.update(world=world, rank=rank, n_samples=N, samples=n, replays=mine[1], recalibrations=mine[2], recaptures=mine[3],
+                     all=dict(replays=summed[1], recalibrations=summed[2], recaptures=summed[3]),
+                     capture_s=t1 - t0, stream_s=t2 - t1, reduce_s=time.perf_counter() - t2)
+    return report, None, metric
 
 
 def _chain(first, rest):

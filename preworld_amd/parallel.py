@@ -16,6 +16,9 @@ RCCL over xGMI on ROCm, 'gloo' in the CPU tests).
   8 ranks = two broadcasts, 164 MB arriving per rank.  xGMI is point-to-point (7 links x ~153 GB/s
   per GPU): one 81.92 MB frame costs ~0.5 ms per link, i.e. comparable to the ~1 ms of
   lift + pre_process it saves -- which is why replicas, not this mode, is the throughput mode.
+* sharded evaluation (harness.evaluate_stream(distributed=True)): rank r scores the samples i % W == r of a split in its own
+  sample stream (eval_shard); after the streams have drained, the integer score tables -- a few KB plus 32 bytes per sample and
+  horizon for the F-score rows -- meet in ONE SUM all-reduce (reduce_eval_counts).  No prediction leaves its rank.
 """
 import torch
 import torch.distributed as dist
@@ -31,6 +34,57 @@ def all_agree(ok, device, group=None, via_host=False):
     t = torch.tensor([1 if ok else 0], dtype=torch.int32, device='cpu' if via_host else device)
     dist.all_reduce(t, op=dist.ReduceOp.MIN, group=group)
     return bool(int(t.item()))
+
+
+def eval_shard(n, rank, world):
+    """the global sample indices rank `rank` of `world` evaluates: i % world == rank, in order.  The order of mmdet's
+    DistributedSampler(shuffle=False) WITHOUT its padding: a padded duplicate would be counted twice in a device table (the
+    reference drops them after gathering the predictions, apis/test.py:193-194)."""
+    return range(rank, n, world)
+
+
+def reduce_eval_counts(metric, rows=None, n_rows=0, counters=(), group=None, via_host=False):
+    """The cross-rank reduction of a sharded evaluation (harness.evaluate_stream(distributed=True)).  Every rank issues the same
+    collectives whatever its sample count (a rank with none passes a fresh metric and an empty row table):
+      * rows given (the F-score is scored): ONE MAX all-reduce of n_rows -> N, the number of rows of the split;
+      * ONE SUM all-reduce of a flat int64 buffer: every horizon's confusion matrix and binary histogram of `metric`
+        (Metric_mIoU_Temporal or Metric_mIoU), its sample counts, `counters` and rows[:N] (zero-padded to N rows).
+    metric is updated in place (its histograms and cnt become the split's).  rows: (n, H, 4) int64, row i = global sample i's
+    F-score counts (zeros where another rank owns the sample).  Returns (list of the summed counters, (N, H, 4) summed rows or None).
+    via_host: stage the buffers through host memory (gloo cannot reduce device tensors; RCCL reduces them on the device)."""
+    subs = list(metric.metrics.values()) if hasattr(metric, 'metrics') else []
+    objs = [metric] + subs                              # the temporal metric and its per-horizon metrics all carry a cnt
+    hists = subs or [metric]
+    dev = hists[0]._hist.device
+    xdev = 'cpu' if via_host else dev
+    N = None
+    if rows is not None:
+        n = torch.tensor([int(n_rows)], dtype=torch.int64, device=xdev)
+        dist.all_reduce(n, op=dist.ReduceOp.MAX, group=group)
+        N = int(n.item())
+        rows = rows[:N]
+        if rows.shape[0] < N:
+            rows = torch.cat([rows, rows.new_zeros((N - rows.shape[0],) + tuple(rows.shape[1:]))])
+    counts = torch.tensor([o.cnt for o in objs] + [int(c) for c in counters], dtype=torch.int64, device=dev)
+    parts = [m._hist.reshape(-1) for m in hists] + [m._occ_hist.reshape(-1) for m in hists] + [counts]
+    if rows is not None:
+        parts.append(rows.reshape(-1).to(dev))
+    flat = torch.cat(parts).to(xdev)
+    dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
+    flat = flat.to(dev)
+    k = 0
+    for m in hists:
+        m._hist.view(-1).copy_(flat[k:k + m._hist.numel()])
+        k += m._hist.numel()
+    for m in hists:
+        m._occ_hist.view(-1).copy_(flat[k:k + m._occ_hist.numel()])
+        k += m._occ_hist.numel()
+    summed = flat[k:k + counts.numel()].tolist()
+    k += counts.numel()
+    for o, c in zip(objs, summed):
+        o.cnt = int(c)
+    out_rows = flat[k:].view(rows.shape) if rows is not None else None
+    return summed[len(objs):], out_rows
 
 
 def owned_states(n_states, rank, world):

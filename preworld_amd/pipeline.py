@@ -348,6 +348,7 @@ class StreamScheduler:
     slot.ranges_ok()     did the last replay stay inside its calibrated activation ranges?
     slot.recalibrate()   re-derive the ranges from the inputs in the static buffers
     slot.commit()        add the last replay's per-sample score table to the running totals
+    slot.commit(index)   (run(..., indexed=True) only) the same for global sample `index` (deferred F-score rows)
     slot.result(buf)     what run() yields for the sample (valid at least until the next next())"""
 
     def __init__(self, slots):
@@ -355,11 +356,13 @@ class StreamScheduler:
         self.replays = 0
         self.recalibrations = 0
 
-    def run(self, samples):
+    def run(self, samples, indexed=False):
+        """indexed=True: the items are (global index, sample) pairs and a finished sample is committed with commit(index)"""
         M = len(self.slots)
-        pending = collections.deque()               # (slot, payload buffer, sample): the sample stays referenced until it is finished
+        pending = collections.deque()               # (slot, payload buffer, sample, index): the sample stays referenced until finished
         parity = [0] * M
-        for i, sample in enumerate(samples):
+        for i, item in enumerate(samples):
+            index, sample = item if indexed else (None, item)
             s = i % M
             slot = self.slots[s]
             slot.stage(sample)
@@ -367,14 +370,14 @@ class StreamScheduler:
             slot.load(sample)
             slot.launch(parity[s])
             self.replays += 1
-            pending.append((slot, parity[s], sample))
+            pending.append((slot, parity[s], sample, index))
             parity[s] ^= 1
             if done is not None:
                 yield done
         while pending:
             yield self._finish(*pending.popleft())
 
-    def _finish(self, slot, buf, sample):
+    def _finish(self, slot, buf, sample, index=None):
         slot.wait()
         if not slot.ranges_ok():
             # a replay outside its window is never counted: repair, replay the same static inputs, check again (run_checked)
@@ -385,7 +388,10 @@ class StreamScheduler:
             slot.wait()
             if not slot.ranges_ok():
                 raise ops._lib.PreworldHipError('activation ranges still outside the window after recalibration')
-        slot.commit()
+        if index is None:
+            slot.commit()
+        else:
+            slot.commit(index)
         return slot.result(buf)
 
 
@@ -530,7 +536,7 @@ class _StreamSlot:
     def recalibrate(self):
         self.cap.recalibrate()
 
-    def commit(self):
+    def commit(self, index=None):
         if self.cap.table is None:
             return
         ms = self.owner.metric_stream
@@ -539,7 +545,9 @@ class _StreamSlot:
                 self.owner.metric.add_counts(self.cap.table, 1, horizons=self.owner.horizons)
             else:
                 self.owner.metric.add_counts(self.cap.table, 1)
-            if self.cap.fs_table is not None:         # every horizon's F-score totals: one pw_occ_fscore_accumulate launch
+            if self.cap.fs_table is not None and index is not None:
+                self.owner._fs_row(index).copy_(self.cap.fs_table)       # deferred: folded later, in index order
+            elif self.cap.fs_table is not None:       # every horizon's F-score totals: one pw_occ_fscore_accumulate launch
                 ops.occ_fscore_accumulate(self.cap.fs_table, self.owner.fs_totals, self.owner.fs_empty)
                 for m in self.owner.fscore.values():
                     m.cnt += 1
@@ -565,6 +573,11 @@ class SampleStream:
       the mIoU mask buffers when the masks agree; another mask gets static buffers of its own, filled from the samples' entry), and
       every finished sample's counts are folded into `self.fscore` = {horizon: metrics.Metric_FScore} on the device.
 
+    run(pairs, indexed=True) takes (global index, sample) pairs (a shard of a larger split, harness.evaluate_stream(distributed=True)):
+    the mIoU tables are added as above, but the F-score counts are NOT folded -- sample i's (H, 4) row is copied into row i of
+    `self.fs_rows`, an (n, H, 4) int64 device table that grows (zero-filled) as indices arrive, for the caller to fold in index order
+    once every shard's rows are in it (ops.occ_fscore_accumulate).
+
     Every replay is range-checked before it counts (a miss: recalibrate, replay the same inputs, check again; still outside the
     window -> PreworldHipError).  Counters: `replays`, `recalibrations`, `recaptures`.
     Stale captures: a fingerprint -- precision() and (data_ptr, _version) of every parameter and buffer -- is taken at capture and
@@ -582,7 +595,7 @@ class SampleStream:
             raise ValueError('SampleStream: PreWorld4DTraj needs example ego states (B,1,21)')
         self.score = dict(score) if score is not None else None
         self.metric = None
-        self.fscore = self.fs_totals = self.fs_empty = None
+        self.fscore = self.fs_totals = self.fs_empty = self.fs_rows = None
         self.horizons, self.mask_key, self.pred_keys, self.fs_mask_key = (), None, None, None
         self._fs_cap = None
         if self.score is not None:
@@ -641,7 +654,18 @@ class SampleStream:
         self._capture()
         self.recaptures += 1
 
-    def run(self, samples):
+    def _fs_row(self, index):
+        """row `index` of the deferred F-score table (on the metric stream; grown by doubling, the new rows zero)"""
+        rows = self.fs_rows
+        if rows is None or index >= rows.shape[0]:
+            n = max(index + 1, 16, 2 * rows.shape[0] if rows is not None else 0)
+            grown = torch.zeros((n, len(self.horizons), 4), dtype=torch.int64, device=self.fs_totals.device)
+            if rows is not None:
+                grown[:rows.shape[0]].copy_(rows)
+            self.fs_rows = rows = grown
+        return rows[index]
+
+    def run(self, samples, indexed=False):
         if not self.slots:
             raise RuntimeError('SampleStream: closed')
         if self._fingerprint() != self._fp:
@@ -649,7 +673,7 @@ class SampleStream:
         self.metric_stream = torch.cuda.current_stream() if self.metric is not None else None     # where the totals are added
         sched = StreamScheduler(self.slots)
         try:
-            for r in sched.run(samples):
+            for r in sched.run(samples, indexed=indexed):
                 yield r
         finally:
             self.replays += sched.replays

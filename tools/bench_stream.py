@@ -14,6 +14,14 @@ raw, score and payload alternate (twice each, about 1.5 s per window at C3) so d
   fscore     the same stream with score['fscore'] (the camera mask): one more pw_occ_fscore launch in every graph and one
              pw_occ_fscore_accumulate per sample
 and prints their ratio and the F-scores of the fscore stream.
+--distributed runs under torch.distributed.run (one process per GPU, RCCL):
+
+    python -m torch.distributed.run --nproc-per-node N tools/bench_stream.py --distributed [--in-flight 2] [--samples 600] [--fscore]
+
+and times harness.evaluate_stream(distributed=True) over a split of --samples samples (rank r scores every W-th one), twice after
+one warm-up call.  Rank 0 prints one JSON line: per rank its scored samples/s (its samples over its stream phase, the slots'
+capture excluded), the aggregate (the split over the slowest rank's stream phase, and over the whole call incl. capture) and the
+seconds from the rank's last sample to the reduced report.  --fscore adds the F-score (deferred rows, folded after the reduction).
 Inputs, GT grids and masks are resident in HBM (N_SETS distinct samples from fixed seeds); evaluate gets the GT as numpy, as
 its callers pass it."""
 import argparse
@@ -96,14 +104,66 @@ def bench_fscore(net, sets, score, M, args):
     print(json.dumps(res), flush=True)
 
 
+def bench_distributed(args):
+    """harness.evaluate_stream(distributed=True) under torch.distributed.run"""
+    import torch.distributed as dist
+    local = int(os.environ.get('LOCAL_RANK', '0'))
+    dev = 'cuda:%d' % local
+    torch.cuda.set_device(local)
+    dist.init_process_group('nccl', device_id=torch.device(dev))
+    try:
+        rank, world = dist.get_rank(), dist.get_world_size()
+        net, _ = bench.build_net(dev, 'C3')
+        sets = make_samples(dev, 2)
+        fs = dict(mask='camera') if args.fscore else None
+
+        def split(n):
+            return [dict(frames=s['frames'], ego=s['ego'], gt=s['gt'], mask_camera=s['mask_camera'])
+                    for s in (sets[i % N_SETS] for i in range(n))]
+        harness.evaluate_stream(net, split(max(args.warmup, world)), in_flight=args.in_flight, fscore=fs, distributed=True)
+        runs = []
+        for _ in range(2):
+            st = {}
+            dist.barrier()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            rep, _, metric = harness.evaluate_stream(net, split(args.samples), in_flight=args.in_flight, fscore=fs,
+                                                     distributed=True, stats=st)
+            st['call_s'] = time.perf_counter() - t0
+            per = [None] * world
+            dist.all_gather_object(per, st)
+            runs.append(dict(
+                per_rank_samples_per_s=[round(p['samples'] / p['stream_s'], 1) if p['samples'] else None for p in per],
+                per_rank_samples=[p['samples'] for p in per],
+                aggregate_samples_per_s=round(args.samples / max(p['stream_s'] for p in per), 1),
+                aggregate_incl_capture_samples_per_s=round(args.samples / max(p['call_s'] for p in per), 1),
+                last_sample_to_report_ms=[round(1e3 * p['reduce_s'], 2) for p in per],
+                capture_s=[round(p['capture_s'], 3) for p in per],
+                recalibrations=st['all']['recalibrations']))
+        if rank == 0:
+            res = dict(config='C3', mode='evaluate_stream(distributed=True)', world=world, backend='nccl', in_flight=args.in_flight,
+                       samples=args.samples, fscore=bool(args.fscore), runs=runs, miou=rep, cnt=metric.cnt,
+                       gt_resident=True, torch=torch.__version__, pw_precision=os.environ.get('PW_PRECISION', 'h2'))
+            if fs is not None:
+                res['fscore_values'] = {h: round(v, 6) for h, v in rep['fscore'].items()}
+            print(json.dumps(res), flush=True)
+    finally:
+        dist.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--in-flight', type=int, default=2)
     ap.add_argument('--samples', type=int, default=600)
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--eval-samples', type=int, default=100)
-    ap.add_argument('--fscore', action='store_true', help='score-only stream with and without the F-score (nothing else)')
+    ap.add_argument('--fscore', action='store_true', help='score-only stream with and without the F-score (nothing else); '
+                    'with --distributed: score the F-score too')
+    ap.add_argument('--distributed', action='store_true', help='evaluate_stream(distributed=True), under torch.distributed.run')
     args = ap.parse_args()
+    if args.distributed:
+        bench_distributed(args)
+        return
     dev = 'cuda:0'
     M = max(1, args.in_flight)
     net, _ = bench.build_net(dev, 'C3')
