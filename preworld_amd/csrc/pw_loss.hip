@@ -216,7 +216,16 @@ __global__ void k_voxel_loss_finish(const double* __restrict__ s, int C, float* 
   out[2] = (float)(bce1(s[99] / s[100]) + bce1(s[99] / s[101]) + bce1(s[102] / s[103]));
 }
 
-// coef = {ga[32], gb[32], gc0, gc1, ce_scale} for pw_voxel_loss_grad; gout = upstream grads of (ce, sem, geo)
+// d BCE(x, 1) / dx as F.binary_cross_entropy's backward takes it, (x - 1) / max(x (1 - x), 1e-12), with the factor 1 - x cancelled:
+// -1 / max(x, 1e-12).  (The two differ only for 1 - x < 1e-12, which sums accumulated in float32 cannot resolve.)  Not -1 / x: where
+// the softmax saturates a ratio underflows to 0 (the forward's log clamp at -100) and -1 / x was -inf -- the voxel's whole gradient
+// NaN -- where the reference's is finite.
+__device__ __forceinline__ double dbce1(double x) { return -1.0 / fmax(x, 1e-12); }
+
+// coef = {ga[32], gb[32], gc0, gc1, ce_scale} for pw_voxel_loss_grad; gout = upstream grads of (ce, sem, geo).
+// sem, class c: precision Spt / Sp, recall Spt / St, specificity (N - Sp - St + Spt) / (N - St); ga multiplies p_c at every voxel of
+// the mask (d / d Sp), gb at the voxels of class c (d / d Spt).  geo: precision I / Sne, recall I / Snt, specificity Se0 / S0 with
+// I = sum nt (1 - pe); d / d pe = gc0 + gc1 nt.
 __global__ void k_voxel_loss_coef(const double* __restrict__ s, int C, const float* __restrict__ gout,
                                   float* __restrict__ coef) {
   const int i = threadIdx.x;
@@ -229,15 +238,17 @@ __global__ void k_voxel_loss_coef(const double* __restrict__ s, int C, const flo
     const int c = i < MAXC ? i : i - MAXC;
     if (c < C && s[35 + c] > 0) {
       const double Sp = s[3 + c], St = s[35 + c], Spt = s[67 + c];
-      const double a_prec = Sp > 0 ? 1.0 / Sp : 0.0;
-      const double a_spec = (N - St > 0) ? 1.0 / (N - Sp - St + Spt) : 0.0;
-      const double b_nom = (Sp > 0 ? -1.0 / Spt : 0.0) - 1.0 / Spt;
-      v = (i < MAXC ? (a_prec + a_spec) : (b_nom - a_spec)) / count * (double)gout[1];
+      const double dp = Sp > 0 ? dbce1(Spt / Sp) : 0.0;
+      const double dr = dbce1(Spt / St);
+      const double ds = N - St > 0 ? dbce1((N - Sp - St + Spt) / (N - St)) / (N - St) : 0.0;
+      const double ga = Sp > 0 ? -dp * (Spt / Sp) / Sp - ds : -ds;
+      const double gb = (Sp > 0 ? dp / Sp : 0.0) + dr / St + ds;
+      v = (i < MAXC ? ga : gb) / count * (double)gout[1];
     }
-  } else if (i == 2 * MAXC) {
-    v = (-1.0 / s[100] - 1.0 / s[102]) * (double)gout[2];
-  } else if (i == 2 * MAXC + 1) {
-    v = (2.0 / s[99] + 1.0 / s[102]) * (double)gout[2];
+  } else if (i < 2 * MAXC + 2) {
+    const double I = s[99], Sne = s[100], Snt = s[101], Se0 = s[102], S0 = s[103];
+    const double dp = dbce1(I / Sne), dr = dbce1(I / Snt), ds = dbce1(Se0 / S0);
+    v = (i == 2 * MAXC ? dp * (I / Sne) / Sne + ds / S0 : -dp / Sne - dr / Snt - ds / S0) * (double)gout[2];
   } else {
     v = (double)gout[0] / s[1];
   }

@@ -603,7 +603,8 @@ PW_API int pw_bn_bwd_apply(const float* x, const float* dy, const float* y, int6
 // ------------------------------------------------------------------------------------
 // Trilinear up-sampling (align_corners=True) of a channels-last map and its adjoint -- the LSSFPN3D of
 // mmdet3d/models/necks/lss_fpn.py:132-148 in training: with the 1x1x1 conv commuted below the up-sampling only the
-// 32-channel maps are interpolated.  Source index / weights exactly as torch's upsample_trilinear3d: src = dst (in-1)/(out-1).
+// 32-channel maps are interpolated.  Source index / weights as torch's upsample_trilinear3d: src = dst (in-1)/(out-1), taken exactly
+// (integer quotient and remainder; a float32 scale times dst is off by up to ~1e-5 in the weight at the 200-voxel axes).
 //   pw_upsample_trilinear_add      hi (+)= up(lo)                        one thread per (hi voxel, 4 channels)
 //   pw_upsample_trilinear_adjoint  dlo = up^T(dhi)                        one axis at a time (k_upsample_axis_adjoint)
 // ------------------------------------------------------------------------------------
@@ -611,16 +612,16 @@ struct UpArgs {
   const float* src;
   float* dst;
   int B, Dl, Hl, Wl, Dh, Hh, Wh, C;
-  float sd, sh, sw;                 // (in - 1) / (out - 1), 0 when out == 1
   int accumulate;
 };
 
-__device__ __forceinline__ void up_axis(int d, float s, int n_in, int& i0, int& i1, float& l0, float& l1) {
-  const float src = s * (float)d;
-  i0 = (int)src;
-  if (i0 > n_in - 1) i0 = n_in - 1;
+// source corners and weights of output index d along an axis of n_in -> n_out: src = d (n_in - 1) / (n_out - 1), 0 when n_out == 1
+__device__ __forceinline__ void up_axis(int d, int n_in, int n_out, int& i0, int& i1, float& l0, float& l1) {
+  const int num = n_in - 1, den = n_out > 1 ? n_out - 1 : 1;
+  const int p = n_out > 1 ? d * num : 0;
+  i0 = p / den;
   i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-  l1 = src - (float)i0;
+  l1 = (float)(p - i0 * den) / (float)den;
   l0 = 1.f - l1;
 }
 
@@ -637,9 +638,9 @@ __global__ void __launch_bounds__(256) k_upsample_add(UpArgs a) {
   const int b = (int)(v / a.Dh);
   int z0, z1, y0, y1, x0, x1;
   float lz0, lz1, ly0, ly1, lx0, lx1;
-  up_axis(z, a.sd, a.Dl, z0, z1, lz0, lz1);
-  up_axis(y, a.sh, a.Hl, y0, y1, ly0, ly1);
-  up_axis(x, a.sw, a.Wl, x0, x1, lx0, lx1);
+  up_axis(z, a.Dl, a.Dh, z0, z1, lz0, lz1);
+  up_axis(y, a.Hl, a.Hh, y0, y1, ly0, ly1);
+  up_axis(x, a.Wl, a.Wh, x0, x1, lx0, lx1);
   const float4* lo = reinterpret_cast<const float4*>(a.src) + (size_t)b * a.Dl * a.Hl * a.Wl * cq + c4;
   auto at = [&](int zz, int yy, int xx) { return lo[(((size_t)zz * a.Hl + yy) * a.Wl + xx) * cq]; };
   const float4 p000 = at(z0, y0, x0), p001 = at(z0, y0, x1), p010 = at(z0, y1, x0), p011 = at(z0, y1, x1);
@@ -653,18 +654,19 @@ __global__ void __launch_bounds__(256) k_upsample_add(UpArgs a) {
   *out = o;
 }
 
-// hi-index range whose corners can include lo index j: floor(s d) in {j - 1, j}
-__device__ __forceinline__ void adj_range(int j, float s, int n_out, int& lo, int& hi) {
+// hi-index range whose corners can include lo index j: floor(s d) in {j - 1, j}, s = (n_in - 1) / (n_out - 1)
+__device__ __forceinline__ void adj_range(int j, int n_in, int n_out, int& lo, int& hi) {
+  const float s = n_out > 1 ? (float)(n_in - 1) / (float)(n_out - 1) : 0.f;
   if (s <= 0.f) { lo = 0; hi = n_out - 1; return; }
   lo = (int)floorf((float)(j - 1) / s) - 1;
   hi = (int)ceilf((float)(j + 1) / s) + 1;
   if (lo < 0) lo = 0;
   if (hi > n_out - 1) hi = n_out - 1;
 }
-__device__ __forceinline__ float adj_weight(int d, int j, float s, int n_in) {
+__device__ __forceinline__ float adj_weight(int d, int j, int n_in, int n_out) {
   int i0, i1;
   float l0, l1;
-  up_axis(d, s, n_in, i0, i1, l0, l1);
+  up_axis(d, n_in, n_out, i0, i1, l0, l1);
   return (i0 == j ? l0 : 0.f) + (i1 == j ? l1 : 0.f);
 }
 
@@ -673,7 +675,7 @@ __device__ __forceinline__ float adj_weight(int d, int j, float s, int n_in) {
 // fine indices whose corners include its coarse index (deterministic, no atomics).  (The 3-D gather of round 3 looped over up to 11^3
 // fine voxels from 80 000 threads: 354 us for the 4x level at 200x200x16; the three passes move 82 + 20 + 5 MB.)
 __global__ void __launch_bounds__(256) k_upsample_axis_adjoint(const float4* __restrict__ src, float4* __restrict__ dst, size_t outer,
-                                                               int n_hi, int n_lo, int inner, float s) {
+                                                               int n_hi, int n_lo, int inner) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= outer * n_lo * inner) return;
   const int i4 = (int)(idx % inner);
@@ -681,11 +683,11 @@ __global__ void __launch_bounds__(256) k_upsample_axis_adjoint(const float4* __r
   const int j = (int)(v % n_lo);
   const size_t o = v / n_lo;
   int lo, hi;
-  adj_range(j, s, n_hi, lo, hi);
+  adj_range(j, n_lo, n_hi, lo, hi);
   const float4* p = src + o * n_hi * inner + i4;
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int d = lo; d <= hi; ++d) {
-    const float w = adj_weight(d, j, s, n_lo);
+    const float w = adj_weight(d, j, n_lo, n_hi);
     if (w == 0.f) continue;
     const float4 g = p[(size_t)d * inner];
     acc.x = fmaf(w, g.x, acc.x); acc.y = fmaf(w, g.y, acc.y); acc.z = fmaf(w, g.z, acc.z); acc.w = fmaf(w, g.w, acc.w);
@@ -695,7 +697,8 @@ __global__ void __launch_bounds__(256) k_upsample_axis_adjoint(const float4* __r
 
 static int up_args(UpArgs& a, const float* src, float* dst, int B, int Dl, int Hl, int Wl, int Dh, int Hh, int Wh, int C,
                    const char* who) {
-  if (!(src && dst && B > 0 && Dl > 0 && Hl > 0 && Wl > 0 && Dh >= Dl && Hh >= Hl && Wh >= Wl && C > 0 && C % 4 == 0)) {
+  if (!(src && dst && B > 0 && Dl > 0 && Hl > 0 && Wl > 0 && Dh >= Dl && Hh >= Hl && Wh >= Wl && C > 0 && C % 4 == 0 &&
+        (int64_t)Dh * Dl < INT32_MAX && (int64_t)Hh * Hl < INT32_MAX && (int64_t)Wh * Wl < INT32_MAX)) {   // up_axis: d (n_in - 1) in int
     pw_set_error("%s: bad arguments", who);
     return PW_EINVAL;
   }
@@ -704,9 +707,6 @@ static int up_args(UpArgs& a, const float* src, float* dst, int B, int Dl, int H
     return PW_EINVAL;
   }
   a.src = src; a.dst = dst; a.B = B; a.Dl = Dl; a.Hl = Hl; a.Wl = Wl; a.Dh = Dh; a.Hh = Hh; a.Wh = Wh; a.C = C;
-  a.sd = Dh > 1 ? (float)(Dl - 1) / (float)(Dh - 1) : 0.f;
-  a.sh = Hh > 1 ? (float)(Hl - 1) / (float)(Hh - 1) : 0.f;
-  a.sw = Wh > 1 ? (float)(Wl - 1) / (float)(Wh - 1) : 0.f;
   a.accumulate = 0;
   return PW_OK;
 }
@@ -737,14 +737,14 @@ PW_API int pw_upsample_trilinear_adjoint(const float* dhi, float* dlo, void* wor
   float4* t2 = t1 + (size_t)B * Dh * Hh * Wl * (C / 4);                            // (B, Dh, Hl, Wl, C)
   hipStream_t st = pw_stream(stream);
   const int cq = C / 4;
-  auto pass = [&](const float4* src, float4* dst, size_t outer, int n_hi, int n_lo, int inner, float s) {
+  auto pass = [&](const float4* src, float4* dst, size_t outer, int n_hi, int n_lo, int inner) {
     const size_t total = outer * n_lo * inner;
     hipLaunchKernelGGL(k_upsample_axis_adjoint, dim3((unsigned)pw_cdiv((int64_t)total, 256)), dim3(256), 0, st, src, dst, outer, n_hi,
-                       n_lo, inner, s);
+                       n_lo, inner);
   };
-  pass(reinterpret_cast<const float4*>(dhi), t1, (size_t)B * Dh * Hh, Wh, Wl, cq, a.sw);
-  pass(t1, t2, (size_t)B * Dh, Hh, Hl, Wl * cq, a.sh);
-  pass(t2, reinterpret_cast<float4*>(dlo), (size_t)B, Dh, Dl, Hl * Wl * cq, a.sd);
+  pass(reinterpret_cast<const float4*>(dhi), t1, (size_t)B * Dh * Hh, Wh, Wl, cq);
+  pass(t1, t2, (size_t)B * Dh, Hh, Hl, Wl * cq);
+  pass(t2, reinterpret_cast<float4*>(dlo), (size_t)B, Dh, Dl, Hl * Wl * cq);
   pw_note_kernel("k_upsample_axis_adjoint");
   PW_CHECK_LAUNCH();
   return PW_OK;

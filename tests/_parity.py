@@ -40,11 +40,18 @@ def check_argmax(name, got, want, ref_logits=None, tie_tol=None, floor=FLOOR):
 
 
 def check_close(name, got, want, rtol, atol=0.0):
-    """max |got - want| <= atol + rtol * max |want|, printed."""
-    got, want = _np(got), _np(want)
-    assert got.shape == want.shape, (name, got.shape, want.shape)
-    scale = float(np.abs(want).max()) if want.size else 0.0
-    err = float(np.abs(got.astype(np.float64) - want.astype(np.float64)).max()) if want.size else 0.0
+    """max |got - want| <= atol + rtol * max |want|, printed.  Two torch tensors are compared in float64 where `want` lives (no
+    host copy of a training-size grid)."""
+    if hasattr(got, 'detach') and hasattr(want, 'detach'):
+        assert tuple(got.shape) == tuple(want.shape), (name, tuple(got.shape), tuple(want.shape))
+        w = want.detach().double()
+        scale = float(w.abs().max()) if w.numel() else 0.0
+        err = float((got.detach().to(w.device).double() - w).abs().max()) if w.numel() else 0.0
+    else:
+        got, want = _np(got), _np(want)
+        assert got.shape == want.shape, (name, got.shape, want.shape)
+        scale = float(np.abs(want).max()) if want.size else 0.0
+        err = float(np.abs(got.astype(np.float64) - want.astype(np.float64)).max()) if want.size else 0.0
     print('[parity] %-44s max|err| %.3e  max|ref| %.3e  rel %.2e (bound %.1e)' % (name, err, scale, err / max(scale, 1e-30), rtol))
     assert REPORT_ONLY or err <= atol + rtol * scale, (name, err, scale, rtol)
     return err
