@@ -493,6 +493,40 @@ int pw_wrs_weights(const float* rays, int64_t n, int frame_id, const float* bala
                    const int32_t* dynamic_class, int n_dyn, float weight_adj, float weight_dyn,
                    float* weights, void* stream);
 
+/* Dense camera views of one attribute grid: ray generation (ray.py:34-45 as pts2ray calls it, :50) fused with the march of
+ * pw_render_rays (nerf_head.py:32-55 sample_ray incl. bda, :165-269 render_one_scene -- inner | cumdist_thres mask, trilinear
+ * look-ups, Raw2Alpha, both fast_color_thres compactions, transmittance scan with the early stop at T < 1e-3 -- and :331-353
+ * render_depth / render_semantic / render_color), one lane per ray, one wave per 8 x 8 pixel tile.  No ray table, nothing per
+ * sample is written.
+ *   K float (V,3,3), c2w float (V,4,4) row-major, BOTH IN DEVICE MEMORY (a captured graph follows new calibrations).
+ *   Pixel mapping: output pixel (i, j) of view v, i < H, j < W, looks through source pixel x = x0 + j stride, y = y0 + i stride:
+ *     dirs = ((x+0.5-K02)/K00, (y+0.5-K12)/K11, 1); rays_d = c2w[:3,:3] . dirs; rays_o = c2w[:3,3]   (pw_pts2ray's arithmetic)
+ *   t float[n_samples] (<= 448), grid (Z,Y,X,grid_channels) fp32 or bf16 (grid_bf16 != 0), channel offsets and the 27 host
+ *   floats of consts_host exactly as pw_render_rays takes them; n_sem = 17.
+ *   Outputs, each optional (NULL), at least one required:
+ *     out_depth float (V,H,W); out_cls uint8 (V,H,W) = argmax of the n_sem rendered semantic sums, lowest index on ties;
+ *     out_sem float (V,H,W,n_sem); out_color float (V,H,W,3); out_last float (V,H,W) = alphainv_last;
+ *     out_rgb8 uint8 (V,H,W,3) = palette[cls], palette uint8 (n_sem+1,3) in device memory.
+ *   min_opacity > 0: a pixel with 1 - alphainv_last < min_opacity gets cls = n_sem (the palette's "nothing there" entry).
+ *   A pixel's value does not depend on the window, stride or view count of the launch it is rendered in.
+ * pw_render_label_views -- LABEL MODE: the grid is uint8 labels, label(x, y, z) = labels[x stride_x + y stride_y + z stride_z]
+ *   (byte strides; the (X,Y,Z)-contiguous semantic_occ arrays have strides (Y Z, Z, 1)).  Same rays, same sample positions, same
+ *   inner | cumdist mask.  A sample's voxel is the one with the largest trilinear weight under the align_corners=True mapping of
+ *   the soft path: floor(u + 0.5) per axis, u the continuous index; outside the grid is a miss.  The first kept sample whose
+ *   label is not empty_idx is the hit: cls = the label, depth = (s_hit + 1e-7) radius with s = 1 - 1/(1+t) (the soft formula with
+ *   all the weight on one sample), alphainv_last = 0.  No hit: cls = empty_idx, depth = 1e-7 radius, alphainv_last = 1.
+ *   out_rgb8 = palette[min(cls, n_palette - 1)], palette uint8 (n_palette,3). */
+int pw_render_views(const float* K, const float* c2w, int n_views, int H, int W, int x0, int y0, int stride,
+                    const float* t, int n_samples, const float* grid, int X, int Y, int Z, int grid_channels,
+                    int c_sigma, int c_sem, int n_sem, int c_rgb, const float* consts_host, float* out_depth,
+                    uint8_t* out_cls, float* out_sem, float* out_color, float* out_last, uint8_t* out_rgb8,
+                    const uint8_t* palette, float min_opacity, int grid_bf16, void* stream);
+int pw_render_label_views(const float* K, const float* c2w, int n_views, int H, int W, int x0, int y0, int stride,
+                          const float* t, int n_samples, const uint8_t* labels, int X, int Y, int Z, int64_t stride_x,
+                          int64_t stride_y, int64_t stride_z, int empty_idx, const float* consts_host, float* out_depth,
+                          uint8_t* out_cls, float* out_last, uint8_t* out_rgb8, const uint8_t* palette, int n_palette,
+                          void* stream);
+
 /* voxel-grid training losses of mmdet3d/models/detectors/loss.py -- CE_ssc_loss
  * (:20-29, class-weighted cross entropy, ignore_index), sem_scal_loss (:32-80) and geo_scal_loss
  * (:83-113) as used by loss_voxel (preworld_temporal_traj.py:176-199) -- forward statistics in one

@@ -24,6 +24,7 @@ EXTRA = {
     'pw_lss.hip': ['-ffp-contract=off'],
     'pw_lss_fused.hip': ['-ffp-contract=off'],
     'pw_render.hip': ['-ffp-contract=off'],
+    'pw_render_views.hip': ['-ffp-contract=off'],
     'pw_stereo.hip': ['-ffp-contract=off'],
 }
 

@@ -571,6 +571,45 @@ class _PreWorldCommon(BEVStereo4DOCC):
             host = host.copy()
         return {k: [host[i]] for i, k in enumerate(cap.host_keys)}
 
+    # ---- rendered camera views of the predicted state(s)
+    def _render_head(self):
+        """the NerfHead whose scene constants and sample table the views use: the model's own, or (a post-finetune config carries
+        none) one with the released geometry of the view transformer's grid (configs/preworld/nuscenes/*-pretrain.py nerf_head)"""
+        if self.nerf_head is not None:
+            return self.nerf_head
+        head = self.__dict__.get('_view_head')
+        if head is None:
+            from .modules import NerfHead
+            gc = self.img_view_transformer.grid_config
+            pcr = [gc['x'][0], gc['y'][0], gc['z'][0], gc['x'][1], gc['y'][1], gc['z'][1]]
+            head = self.__dict__['_view_head'] = NerfHead(point_cloud_range=pcr, voxel_size=gc['x'][2], radius=39)
+        return head
+
+    @torch.no_grad()
+    def _render_result(self, res, frames, intrins, sensor2keyegos, image_hw, stride=1, outputs=None, bda=None, **kw):
+        """res: what simple_test_from_lift returned.  One view set per state, keyed '<output><suffix>' with the suffix of the state's
+        `semantic_occ<suffix>` key.  Pre-train models (if_post_finetune=False): the state's features -> attr_mlp -> packed grid ->
+        the soft renderer.  Post-finetune models: the state's uint8 grid from the OccHead, still on the device -> label mode."""
+        head = self._render_head()
+        if bda is None:
+            bda = frames[0]['bda'].reshape(-1, 3, 3)[0]
+        bda = bda.cpu()                      # ONE read-back per call (the scene constants are host arguments of the kernel), not one per state
+        if outputs is None:
+            outputs = ('depth', 'cls') if self.if_post_finetune else ('depth', 'cls', 'color')
+        names = [k for k in res if k.startswith('semantic_occ')]
+        out = {}
+        for i, name in enumerate(names):
+            sfx = name[len('semantic_occ'):]
+            if self.if_post_finetune:
+                views = head.render_label_views(res[name][0], intrins, sensor2keyegos, image_hw, bda=bda, stride=stride,
+                                                empty_idx=self.empty_idx, outputs=outputs, **kw)
+            else:
+                f = res['voxel_feats'][i]
+                grid = self.attributes_cl(ops.h2_to_f32(f) if isinstance(f, ops.H2) else f)[0]
+                views = head.render_views(grid, intrins, sensor2keyegos, image_hw, bda=bda, stride=stride, outputs=outputs, **kw)
+            out.update({k + sfx: v for k, v in views.items()})
+        return out
+
     @staticmethod
     def _to_numpy(res):
         """the reference's payload: every grid a numpy uint8 (X,Y,Z) array (one D2H copy for all of them)"""
@@ -602,6 +641,12 @@ class PreWorld(_PreWorldCommon):
         res['semantic_occ'] = [occ[0]]
         res['geo_occ'] = [geo[0]]
         return res
+
+    def render_forecast(self, frames, intrins, sensor2keyegos, image_hw, stride=1, outputs=None, **kw):
+        """The single predicted state as the cameras would see it: {'depth', 'cls', 'color', ...} -> (V,h,w[,3]) device tensors
+        (_render_result; NerfHead.render_views / render_label_views).  intrins (V,3,3), sensor2keyegos (V,4,4), image_hw = (H, W) of
+        the source images, every `stride`-th pixel.  simple_test is not involved and returns what it did."""
+        return self._render_result(self.simple_test_from_lift(frames), frames, intrins, sensor2keyegos, image_hw, stride, outputs, **kw)
 
     def simple_test(self, points, img_metas, img=None, rescale=False, **kwargs):
         frames = self.lift_inputs_from_images(self.prepare_inputs(img, stereo=True))
@@ -783,6 +828,15 @@ class PreWorld4DTraj(_PreWorldCommon):
             res['geo_occ_%ds' % name] = [geo[0]]
         res['voxel_feats'] = feats
         return res
+
+    def render_forecast(self, frames, ego, intrins, sensor2keyegos, image_hw, n_steps=6, stride=1, outputs=None, **kw):
+        """Every predicted state as the cameras would see it: {'depth_{k}s', 'cls_{k}s', 'color_{k}s', ...}, one (V,h,w[,3]) device
+        tensor per state and output, k numbered as simple_test numbers its keys (0..6 post-finetune, 0, 2..7 on the attribute-MLP
+        branch).  frames / ego as simple_test_from_lift takes them; intrins (V,3,3), sensor2keyegos (V,4,4), image_hw = (H, W) of
+        the source images, every `stride`-th pixel.  Pre-train models render depth / semantics / colour through the soft renderer,
+        post-finetune models their uint8 grids through label mode (depth / cls), on the device, before any payload copy."""
+        return self._render_result(self.simple_test_from_lift(frames, ego, n_steps), frames, intrins, sensor2keyegos, image_hw, stride,
+                                   outputs, **kw)
 
     # ---- preworld_temporal_traj.py:212-370 with the reference's signature: images + kwargs['temporal_ego_states']
     def set_epoch(self, epoch):                                         # :150-151, called by the reference's epoch hook

@@ -921,6 +921,32 @@ class NerfHead(nn.Module):
                                self.t_table(grid.device), grid, self.consts(bda.cpu()),
                                want_debug=want_debug)
 
+    @staticmethod
+    def _view_geometry(intrins, sensor2keyegos, image_hw, stride, origin):
+        """(V,3,3) / (V,4,4) fp32 device tensors and the output (H, W): every `stride`-th source pixel from `origin` = (x0, y0)"""
+        K = intrins.reshape(-1, 3, 3).float().contiguous()
+        c2w = sensor2keyegos.reshape(-1, 4, 4).float().contiguous()
+        H, W = int(image_hw[0]), int(image_hw[1])
+        hw = (-(-(H - int(origin[1])) // int(stride)), -(-(W - int(origin[0])) // int(stride)))
+        return K, c2w, hw
+
+    @torch.no_grad()
+    def render_views(self, grid, intrins, sensor2keyegos, image_hw, bda=None, stride=1, origin=(0, 0), **kw):
+        """What the cameras would see of the packed (Z,Y,X,24) attribute grid: intrins (V,3,3), sensor2keyegos (V,4,4) (camera ->
+        the frame the grid lives in), image_hw = (H, W) of the SOURCE images; every `stride`-th pixel from `origin` = (x0, y0) is
+        rendered (ops.render_views: ray generation + the march of `render` in one launch).  bda (3,3) on the host, default
+        identity.  kw: outputs, palette, min_opacity.  Returns {'depth' (V,h,w), 'cls' u8 (V,h,w), 'color' (V,h,w,3), ...}."""
+        K, c2w, hw = self._view_geometry(intrins, sensor2keyegos, image_hw, stride, origin)
+        return ops.render_views(grid, K, c2w, hw, self.consts(torch.eye(3) if bda is None else bda.cpu()), self.t_table(grid.device),
+                                stride=stride, origin=origin, **kw)
+
+    @torch.no_grad()
+    def render_label_views(self, occ_u8, intrins, sensor2keyegos, image_hw, bda=None, stride=1, origin=(0, 0), **kw):
+        """render_views of a uint8 (X,Y,Z) label grid (first non-empty voxel along the ray; ops.render_label_views)."""
+        K, c2w, hw = self._view_geometry(intrins, sensor2keyegos, image_hw, stride, origin)
+        return ops.render_label_views(occ_u8, K, c2w, hw, self.consts(torch.eye(3) if bda is None else bda.cpu()),
+                                      self.t_table(occ_u8.device), stride=stride, origin=origin, **kw)
+
     def compute_loss(self, out, target_depth, target_semantic, target_color, suffix=''):
         """nerf_head.py:271-329 on the fused kernel's outputs."""
         losses = {}

@@ -1291,6 +1291,83 @@ def render_rays(rays_o, rays_d, t, grid, consts, c_sigma=0, c_sem=2, n_sem=17, c
     return out
 
 
+_VIEW_OUTPUTS = {'depth': (_f32, ()), 'cls': (torch.uint8, ()), 'sem': (_f32, (17,)), 'color': (_f32, (3,)),
+                 'alphainv_last': (_f32, ()), 'rgb8': (torch.uint8, (3,))}
+
+
+def _view_args(who, first, K, c2w, hw, outputs, allowed, palette):
+    """shared checks of render_views / render_label_views (a host tensor raises PreworldHipError here: the package has no CPU path),
+    then the output tensors; the callers check what is theirs BEFORE calling this, so nothing is allocated for a refused call"""
+    if not isinstance(first, torch.Tensor) or not first.is_cuda:
+        raise _lib.PreworldHipError('%s: the grid must be a CUDA(HIP) tensor (there is no CPU fallback)' % who)
+    if K.dim() != 3 or tuple(K.shape[1:]) != (3, 3) or c2w.dim() != 3 or tuple(c2w.shape[1:]) != (4, 4) or K.shape[0] != c2w.shape[0]:
+        raise _lib.PreworldHipError('%s: K must be (V,3,3) and c2w (V,4,4), got %s and %s' % (who, tuple(K.shape), tuple(c2w.shape)))
+    outputs = tuple(outputs)
+    bad = [o for o in outputs if o not in allowed]
+    if bad or not outputs:
+        raise _lib.PreworldHipError('%s: outputs must be a non-empty subset of %s, got %s' % (who, allowed, outputs))
+    if 'rgb8' in outputs:
+        if palette is None:
+            raise _lib.PreworldHipError('%s: output rgb8 needs a palette' % who)
+        _chk(palette, torch.uint8, 'palette')
+        if palette.dim() != 2 or palette.shape[1] != 3:
+            raise _lib.PreworldHipError('%s: palette must be (n, 3) uint8' % who)
+    V, (H, W) = K.shape[0], hw
+    out = {o: torch.empty((V, int(H), int(W)) + _VIEW_OUTPUTS[o][1], device=first.device, dtype=_VIEW_OUTPUTS[o][0]) for o in outputs}
+    return V, int(H), int(W), out
+
+
+def render_views(grid, K, c2w, hw, consts, t, stride=1, origin=(0, 0), outputs=('depth', 'cls', 'color'), palette=None,
+                 min_opacity=0.0, c_sigma=0, c_sem=2, n_sem=17, c_rgb=19):
+    """V dense camera views of the packed (Z,Y,X,GC) attribute grid in ONE launch (pw_render_views: the rays of ray.py:34-45,50
+    generated per pixel + the march of render_rays, one lane per ray).  K (V,3,3), c2w (V,4,4) device tensors; hw = (H, W) of
+    the OUTPUT; output pixel (i, j) looks through source pixel (x, y) = (origin[0] + j stride, origin[1] + i stride).
+    consts / t as render_rays.  outputs: any of depth (V,H,W), cls u8 (V,H,W), sem (V,H,W,17), color (V,H,W,3),
+    alphainv_last (V,H,W), rgb8 u8 (V,H,W,3) = palette[cls] with palette u8 (n_sem+1,3) on the device.  min_opacity > 0:
+    pixels with 1 - alphainv_last below it get cls = n_sem.  Returns a dict of device tensors; no host sync (capturable)."""
+    if not isinstance(grid, torch.Tensor) or not grid.is_cuda:
+        raise _lib.PreworldHipError('render_views: the grid must be a CUDA(HIP) tensor (there is no CPU fallback)')
+    bf16 = grid.dtype == torch.bfloat16
+    if not bf16 and grid.dtype != _f32:
+        raise _lib.PreworldHipError('render_views: the packed grid must be float32 or bfloat16 (uint8 labels go through render_label_views)')
+    if grid.dim() != 4 or not grid.is_contiguous():
+        raise _lib.PreworldHipError('render_views: grid must be a contiguous (Z,Y,X,GC) tensor')
+    if palette is not None and 'rgb8' in outputs and palette.shape[0] != n_sem + 1:
+        raise _lib.PreworldHipError('render_views: palette must have n_sem + 1 = %d rows' % (n_sem + 1))
+    V, H, W, out = _view_args('render_views', grid, K, c2w, hw, outputs, tuple(_VIEW_OUTPUTS), palette)
+    Z, Y, X, GC = grid.shape
+    ch = (ctypes.c_float * 27)(*[float(v) for v in consts])
+    _lib.call('pw_render_views', _chk(K, _f32, 'K'), _chk(c2w, _f32, 'c2w'), V, H, W, int(origin[0]), int(origin[1]), int(stride),
+              _chk(t, _f32, 't'), t.numel(), _p(grid), X, Y, Z, GC, c_sigma, c_sem, n_sem, c_rgb, ch, _p(out.get('depth')),
+              _p(out.get('cls')), _p(out.get('sem')), _p(out.get('color')), _p(out.get('alphainv_last')), _p(out.get('rgb8')),
+              _p(palette), float(min_opacity), int(bf16), _stream())
+    return out
+
+
+def render_label_views(occ_u8, K, c2w, hw, consts, t, empty_idx=17, stride=1, origin=(0, 0), outputs=('depth', 'cls'), palette=None):
+    """render_views in LABEL MODE (pw_render_label_views): occ_u8 is a uint8 (X,Y,Z) label grid on the device with ANY strides
+    (the (X,Y,Z)-contiguous semantic_occ_* arrays, or the permuted view of the OccHead's (Z,Y,X) buffer).  Same rays, samples and
+    inner | cumdist mask as the soft path; a sample's voxel is floor(u + 0.5) per axis of the align_corners=True continuous
+    index u (outside = miss); the first kept sample whose label is not empty_idx is the hit: cls = label,
+    depth = (s_hit + 1e-7) radius, alphainv_last = 0; no hit: cls = empty_idx, depth = 1e-7 radius, alphainv_last = 1.
+    outputs: any of depth, cls, alphainv_last, rgb8 (= palette[cls])."""
+    if not isinstance(occ_u8, torch.Tensor) or not occ_u8.is_cuda:
+        raise _lib.PreworldHipError('render_label_views: the label grid must be a CUDA(HIP) tensor (there is no CPU fallback)')
+    if occ_u8.dtype != torch.uint8 or occ_u8.dim() != 3:
+        raise _lib.PreworldHipError('render_label_views: the label grid must be a uint8 (X,Y,Z) tensor')
+    sx, sy, sz = occ_u8.stride()
+    if min(sx, sy, sz) <= 0:
+        raise _lib.PreworldHipError('render_label_views: the label grid must have positive strides')
+    V, H, W, out = _view_args('render_label_views', occ_u8, K, c2w, hw, outputs, ('depth', 'cls', 'alphainv_last', 'rgb8'), palette)
+    X, Y, Z = occ_u8.shape
+    ch = (ctypes.c_float * 27)(*[float(v) for v in consts])
+    _lib.call('pw_render_label_views', _chk(K, _f32, 'K'), _chk(c2w, _f32, 'c2w'), V, H, W, int(origin[0]), int(origin[1]),
+              int(stride), _chk(t, _f32, 't'), t.numel(), _ptr(occ_u8), X, Y, Z, sx, sy, sz, int(empty_idx), ch,
+              _p(out.get('depth')), _p(out.get('cls')), _p(out.get('alphainv_last')), _p(out.get('rgb8')), _p(palette),
+              0 if palette is None else palette.shape[0], _stream())
+    return out
+
+
 def render_rays_backward(rays_o, rays_d, t, grid, consts, g_depth, g_sem, g_rgb, g_last, g_weights=None, c_sigma=0, c_sem=2,
                          n_sem=17, c_rgb=19, grad_grid=None, algo=None, max_entries=0):
     """Backward of render_rays: gradient of the packed (Z,Y,X,GC) grid given the gradients of depth (R), semantic (R,17),
