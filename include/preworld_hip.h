@@ -493,6 +493,57 @@ int pw_wrs_weights(const float* rays, int64_t n, int frame_id, const float* bala
                    const int32_t* dynamic_class, int n_dyn, float weight_adj, float weight_dyn,
                    float* weights, void* stream);
 
+/* LSS depth supervision of the fine-tune step on the GPU (pw_depth_sup.hip): one lidar sweep in, depth maps / depth labels /
+ * the depth loss and its gradient out.  No dense map crosses PCIe and nothing here synchronises the host.
+ *
+ * The sweep, common to pw_lidar_depth_maps and pw_lidar_depth_labels:
+ *   points    float[n_points][point_stride], x y z first (point_stride >= 3); the sweeps of the B samples back to back
+ *   offsets   int32[B + 1] IN DEVICE MEMORY: sample b owns points offsets[b] .. offsets[b+1]-1; rows outside
+ *             [offsets[0], offsets[B]) are ignored, so a captured graph replays on a sweep of another length copied into
+ *             the same buffer.  NULL: B == 1 and every row belongs to it.
+ *   lidar2img float[B N][3][4], post_rot float[B N][3][3], post_tran float[B N][3], device memory, view v = b N + n
+ *   H, W      size of the (augmented) input image; downsample as PointToMultiViewDepth's; [d0, d1) = grid_config['depth'][:2],
+ *             0 < d0 < d1 (the minimum is an integer minimum on the bit pattern, which needs positive depths)
+ * pw_lidar_depth_maps (mmdet3d/datasets/pipelines/loading.py:768-787 points2depthmap, :828-843 the projection of __call__):
+ *   q = p . R^T + t (R | t = lidar2img; the host's sgemm: fma(p2, R2, fma(p1, R1, p0 R0)), then + t);  q.xy /= q.z;
+ *   (u, v, d) = q . post_rot^T + post_tran (the depth row passes through it as well);  cx = rint(u / downsample),
+ *   cy = rint(v / downsample), half to even;  kept iff 0 <= cx < w, 0 <= cy < h, d0 <= d < d1 (w = W / downsample, ...);
+ *   depth_maps float[B N][h][w] = the smallest kept d of the pixel, 0 where nothing lands.
+ *   The reference keeps the first point of each pixel after an UNSTABLE argsort on float32(cy w + cx + d / 100): where two
+ *   depths of one pixel round to the same key it may keep either; this takes the exact minimum.
+ * pw_lidar_depth_labels: the same projection; the minimum is taken per loss_downsample x loss_downsample cell of the rounded
+ *   pixel (cell = pixel / loss_downsample, which must divide h and w) and binned as pw_depth_map_labels bins it.  What comes out
+ *   equals pw_depth_map_labels(pw_lidar_depth_maps(...)) without the maps being written.  labels int32[B N][h/ld][w/ld].
+ * pw_depth_map_labels (mmdet3d/models/necks/view_transformer.py:736-773 get_downsampled_gt_depth, sid=False):
+ *   depth_maps float[n_views][H][W] -> labels int32[n_views][H/downsample][W/downsample]:  m = min over the patch of
+ *   (x == 0 ? 1e5 : x);  g = (m - float(d0 - dstep)) / dstep in float32;  label = 0 <= g < D + 1 ? (long)g - 1 : -1.
+ *   label k >= 0 is column k of the reference's one-hot (its argmax), -1 is its all-zero row (fg_mask false).  W <= 12288.
+ *   Equal to the reference's labels bit for bit where dstep is a power of two (the released 0.5: d0 - dstep is exact and
+ *   the division is); for another dstep torch may divide by multiplying with the reciprocal and forms d0 - dstep in double,
+ *   and a depth on a bin edge can then land one bin off.
+ * pw_depth_bce_fwd / _bwd (view_transformer.py:775-789 get_depth_loss): the prediction stays in its own layout,
+ *   pred float[BN][D][hw] (softmax over D), labels int32[BN][hw]:
+ *   loss = weight * sum_{cells with label k >= 0} ( -max(log p_k, -100) - sum_{j != k} max(log(1 - p_j), -100) ) / max(1, n_fg)
+ *   (F.binary_cross_entropy's clamp), n_fg = #(label >= 0), both written to device memory (float[1], int32[1]).  The sum
+ *   is taken in double, per block in a fixed order and over the blocks in a fixed order by one finishing block: the same
+ *   bits on every run.  ws: pw_depth_bce_ws_bytes(BN hw) bytes of scratch, 8-byte aligned.
+ *   _bwd: grad_pred (layout of pred) = (grad_out[0] weight / max(1, n_fg[0])) (p - y) / max((1 - p) p, 1e-12) on cells with a
+ *   label (ATen's binary_cross_entropy_backward), 0 elsewhere; grad_out float[1] and n_fg are read from device memory. */
+int pw_lidar_depth_maps(const float* points, int64_t n_points, int point_stride, const int32_t* offsets, int B, int N,
+                        const float* lidar2img, const float* post_rot, const float* post_tran, int H, int W,
+                        int downsample, float d0, float d1, float* depth_maps, void* stream);
+int pw_lidar_depth_labels(const float* points, int64_t n_points, int point_stride, const int32_t* offsets, int B, int N,
+                          const float* lidar2img, const float* post_rot, const float* post_tran, int H, int W,
+                          int downsample, int loss_downsample, float d0, float d1, float dstep, int D, int32_t* labels,
+                          void* stream);
+int pw_depth_map_labels(const float* depth_maps, int n_views, int H, int W, int downsample, float d0, float dstep, int D,
+                        int32_t* labels, void* stream);
+size_t pw_depth_bce_ws_bytes(int64_t n_cells);
+int pw_depth_bce_fwd(const float* pred, const int32_t* labels, int BN, int D, int64_t hw, float weight, void* ws,
+                     float* loss, int32_t* n_fg, void* stream);
+int pw_depth_bce_bwd(const float* pred, const int32_t* labels, const float* grad_out, const int32_t* n_fg, int BN, int D,
+                     int64_t hw, float weight, float* grad_pred, void* stream);
+
 /* Dense camera views of one attribute grid: ray generation (ray.py:34-45 as pts2ray calls it, :50) fused with the march of
  * pw_render_rays (nerf_head.py:32-55 sample_ray incl. bda, :165-269 render_one_scene -- inner | cumdist_thres mask, trilinear
  * look-ups, Raw2Alpha, both fast_color_thres compactions, transmittance scan with the early stop at T < 1e-3 -- and :331-353

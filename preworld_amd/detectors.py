@@ -230,13 +230,27 @@ class BEVStereo4DOCC(nn.Module):
             raise NotImplementedError('loss_occ=%r: only the plain softmax CrossEntropyLoss of the released configs is built' % (cfg,))
         prepared = self.prepare_inputs(img_inputs, stereo=True)
         feat_cl, depth = self._bev_feat_train(prepared)
-        losses = {'loss_depth': self.img_view_transformer.get_depth_loss(kwargs['gt_depth'], depth)}
+        losses = {'loss_depth': self._lss_depth_loss(depth, prepared, points, kwargs)}
         v = as_f32(self.final_conv.forward_cl(feat_cl)).permute(0, 3, 2, 1, 4)      # (B,X,Y,Z,C) view (:318)
         occ_pred = self.predicter(v) if self.use_predicter else v
         sem = kwargs['voxel_semantics'].long().reshape(-1)
         losses['loss_occ'] = float(cfg.get('loss_weight', 1.0)) * nn.functional.cross_entropy(
             occ_pred.reshape(-1, self.num_classes), sem, reduction='mean')
         return losses
+
+    def _lss_depth_loss(self, depth, prepared, points, kwargs):
+        """The LSS depth term of the three forward_trains.  With only `gt_depth=` (the reference's dense maps): get_depth_loss, as
+        before.  With `gt_depth_labels=` ((B*N,h,w) int32, e.g. from transforms.PointToMultiViewDepth(labels_downsample=...)), or
+        with the sweep itself, `points=` and `lidar2img=` (B,N,4,4): labels and loss on the device (pw_depth_sup.hip) -- no dense
+        map, no host synchronisation.  points: a list of B (P_b, >=3) tensors, or one tensor with `points_offsets=`."""
+        vt = self.img_view_transformer
+        labels = kwargs.get('gt_depth_labels')
+        if labels is None and points is not None and kwargs.get('lidar2img') is not None:
+            labels = vt.get_depth_labels(points=points, lidar2img=kwargs['lidar2img'], post_rots=prepared[4][0],
+                                         post_trans=prepared[5][0], offsets=kwargs.get('points_offsets'))
+        if labels is None:
+            return vt.get_depth_loss(kwargs['gt_depth'], depth)
+        return vt.get_depth_loss_from_labels(labels, depth)
 
     # ---- the frame loop of the training step (shared by the three detectors)
     def _bev_feat_train(self, img_inputs):
@@ -664,7 +678,7 @@ class PreWorld(_PreWorldCommon):
         feat_cl, depth = self._bev_feat_train(prepared)
         out = self.forward_train_from_feats(feat_cl, bda=prepared[6], **kwargs)
         if self.use_lss_depth_loss:
-            out['loss_lss_depth'] = self.img_view_transformer.get_depth_loss(kwargs['gt_depth'], depth)
+            out['loss_lss_depth'] = self._lss_depth_loss(depth, prepared, points, kwargs)
         return out
 
 
@@ -862,7 +876,7 @@ class PreWorld4DTraj(_PreWorldCommon):
         v = as_f32(self.final_conv.forward_cl(feat_cl))                 # (B,Z,Y,X,C)
         losses = {}
         if self.use_lss_depth_loss:
-            losses['loss_lss_depth'] = self.img_view_transformer.get_depth_loss(kwargs['gt_depth'], depth)
+            losses['loss_lss_depth'] = self._lss_depth_loss(depth, prepared, points, kwargs)
         bda = prepared[6]
         losses.update(self._voxel_losses_train(v, interval=0, voxel_semantics=kwargs['voxel_semantics'],
                                                rays=kwargs.get('rays'), bda=bda))

@@ -254,6 +254,26 @@ class LSSViewTransformerBEVDepth(LSSViewTransformer):
         loss = torch.nn.functional.binary_cross_entropy(depth_preds[fg_mask], depth_labels[fg_mask], reduction='none')
         return self.loss_depth_weight * (loss.sum() / max(1.0, fg_mask.sum()))
 
+    # ---- the same supervision on the device (pw_depth_sup.hip): labels instead of a one-hot, from a dense map or from the sweep
+    def get_depth_labels(self, gt_depth=None, points=None, lidar2img=None, post_rots=None, post_trans=None, offsets=None):
+        """(B*N, h, w) int32 depth labels: bin k >= 0 of get_downsampled_gt_depth's one-hot, -1 where its row is all zero.
+        Either from a dense gt_depth (B,N,H,W) (ops.depth_map_labels: the reference's labels exactly), or from the lidar sweep
+        itself -- points (a (P,>=3) tensor, with int32 device `offsets` for B > 1, or a list of B tensors), lidar2img (B,N,4,4) and
+        the key frame's post_rots (B,N,3,3) / post_trans (B,N,3) (ops.lidar_depth_labels: PointToMultiViewDepth at downsample 1
+        and the patch minimum in one pass; the dense maps are never made)."""
+        depth_cfg = self.grid_config['depth']
+        if gt_depth is not None:
+            return ops.depth_map_labels(gt_depth, self.downsample, depth_cfg, self.D)
+        if points is None or lidar2img is None or post_rots is None or post_trans is None:
+            raise ValueError('get_depth_labels needs gt_depth=, or points= with lidar2img=, post_rots= and post_trans=')
+        return ops.lidar_depth_labels(points, lidar2img, post_rots, post_trans, self.input_size, depth_cfg, self.downsample, self.D,
+                                      offsets=offsets)
+
+    def get_depth_loss_from_labels(self, labels, depth_preds):
+        """get_depth_loss on labels (ops.DepthBCE): depth_preds (B*N, D, h, w) is read and differentiated in its own layout; no
+        permute copy, no one-hot, no mask indexing and no host synchronisation."""
+        return ops.depth_bce(depth_preds, labels, self.loss_depth_weight)
+
     # ---- view_transformer.py:791-804
     def forward(self, input, stereo_metas=None, depth_gt=None):
         x, mlp_input = input[0], input[7]

@@ -1038,6 +1038,117 @@ def wrs_weights(rays, frame_id, balance_weight, dynamic_class, weight_adj=0.3, w
     return w
 
 
+# ------------------------------------------------------------------------------ depth supervision from the sweep
+def _sweep_args(points, offsets, lidar2img, post_rots, post_trans):
+    """-> (points (P,C) f32, offsets int32 (B+1) device tensor or None, B, N, lidar2img (B N,3,4), post_rots (B N,3,3),
+    post_trans (B N,3)).  points: one (P,C) tensor (with `offsets`, or alone for B == 1) or a list of B per-sample tensors."""
+    if lidar2img.dim() != 4 or lidar2img.shape[-1] != 4 or lidar2img.shape[-2] not in (3, 4):
+        raise _lib.PreworldHipError('lidar2img must be (B,N,4,4) or (B,N,3,4), got %s' % (tuple(lidar2img.shape),))
+    B, N = lidar2img.shape[:2]
+    if isinstance(points, (list, tuple)):
+        if len(points) != B:
+            raise _lib.PreworldHipError('%d sweeps for %d samples' % (len(points), B))
+        if offsets is None and B > 1:                # offsets are known on the host here: one small H2D copy, nothing read back
+            counts = [0] + [int(p.shape[0]) for p in points]
+            offsets = torch.tensor(np.cumsum(counts), dtype=_i32).to(points[0].device, non_blocking=True)
+        points = torch.cat([p.float() for p in points], 0) if B > 1 else points[0]
+    if points.dim() != 2 or points.shape[1] < 3:
+        raise _lib.PreworldHipError('points must be (P, >=3), got %s' % (tuple(points.shape),))
+    if offsets is None and B != 1:
+        raise _lib.PreworldHipError('B = %d samples in one points tensor need offsets (int32, B + 1, on the device)' % B)
+    if offsets is not None and (offsets.dtype != _i32 or offsets.numel() != B + 1):
+        raise _lib.PreworldHipError('offsets must be int32 with B + 1 = %d entries' % (B + 1))
+    l2i = lidar2img[..., :3, :].float().contiguous().view(B * N, 3, 4)
+    return (points.float().contiguous(), offsets, B, N, l2i, post_rots.float().contiguous().view(B * N, 3, 3),
+            post_trans.float().contiguous().view(B * N, 3))
+
+
+def lidar_depth_maps(points, lidar2img, post_rots, post_trans, image_hw, depth_range, downsample=1, offsets=None):
+    """PointToMultiViewDepth (mmdet3d/datasets/pipelines/loading.py:762-844) on the device: the sweep(s) `points` projected into
+    the B x N views -> gt_depth (B, N, H // downsample, W // downsample), per pixel the exact minimum depth in
+    [depth_range[0], depth_range[1]), 0 where nothing lands.  lidar2img (B,N,4,4) is what the reference composes from the four
+    poses and the intrinsics (transforms.compose_lidar2img)."""
+    pts, offsets, B, N, l2i, pr, pt = _sweep_args(points, offsets, lidar2img, post_rots, post_trans)
+    H, W = int(image_hw[0]), int(image_hw[1])
+    out = torch.empty(B, N, H // downsample, W // downsample, device=pts.device, dtype=_f32)
+    _lib.call('pw_lidar_depth_maps', _chk(pts, _f32, 'points'), pts.shape[0], pts.shape[1],
+              _chk(offsets, _i32, 'offsets') if offsets is not None else None, B, N, _chk(l2i, _f32, 'lidar2img'),
+              _chk(pr, _f32, 'post_rots'), _chk(pt, _f32, 'post_trans'), H, W, int(downsample), float(depth_range[0]),
+              float(depth_range[1]), _p(out), _stream())
+    return out
+
+
+def lidar_depth_labels(points, lidar2img, post_rots, post_trans, image_hw, depth_cfg, loss_downsample, D=None, downsample=1,
+                       offsets=None):
+    """The depth labels of get_downsampled_gt_depth straight from the sweep: (B*N, h, w) int32, label k >= 0 = depth bin k of the
+    minimum depth landing in the cell, -1 = no label.  depth_cfg = grid_config['depth'] = [d0, d1, dstep]; equals
+    depth_map_labels(lidar_depth_maps(...)) without the maps."""
+    pts, offsets, B, N, l2i, pr, pt = _sweep_args(points, offsets, lidar2img, post_rots, post_trans)
+    H, W = int(image_hw[0]), int(image_hw[1])
+    d0, d1, dstep = [float(v) for v in depth_cfg]
+    D = int(D) if D is not None else int(round((d1 - d0) / dstep))
+    ld = int(loss_downsample)
+    out = torch.empty(B * N, H // downsample // ld, W // downsample // ld, device=pts.device, dtype=_i32)
+    _lib.call('pw_lidar_depth_labels', _chk(pts, _f32, 'points'), pts.shape[0], pts.shape[1],
+              _chk(offsets, _i32, 'offsets') if offsets is not None else None, B, N, _chk(l2i, _f32, 'lidar2img'),
+              _chk(pr, _f32, 'post_rots'), _chk(pt, _f32, 'post_trans'), H, W, int(downsample), ld, d0, d1, dstep, D, _p(out),
+              _stream())
+    return out
+
+
+def depth_map_labels(gt_depth, downsample, depth_cfg, D=None):
+    """get_downsampled_gt_depth (view_transformer.py:736-773, sid=False) as labels: gt_depth (B,N,H,W) or (B*N,H,W) float32 ->
+    (B*N, H // downsample, W // downsample) int32; label k >= 0 is the hot column of the reference's one-hot row, -1 its all-zero
+    row."""
+    g = gt_depth.float().contiguous()
+    H, W = g.shape[-2:]
+    V = g.numel() // (H * W)
+    d0, d1, dstep = [float(v) for v in depth_cfg]
+    D = int(D) if D is not None else int(round((d1 - d0) / dstep))
+    out = torch.empty(V, H // downsample, W // downsample, device=g.device, dtype=_i32)
+    _lib.call('pw_depth_map_labels', _chk(g, _f32, 'gt_depth'), V, H, W, int(downsample), d0, dstep, D, _p(out), _stream())
+    return out
+
+
+class DepthBCE(torch.autograd.Function):
+    """get_depth_loss (view_transformer.py:775-789) on labels: pred (B*N, D, h, w) softmaxed depth in its own layout, labels
+    (B*N, h, w) int32 -> weight * BCE sum over the labelled cells / max(1, n_fg), a 0-dim tensor.  n_fg stays in device memory
+    (nothing synchronises, so the term can sit inside a captured step); the sum is bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, pred, labels, weight):
+        BN, D = pred.shape[:2]
+        hw = pred[0, 0].numel()
+        if pred.dtype != _f32:       # the gradient comes back as float32 in this layout; autocast callers cast the softmax first
+            raise _lib.PreworldHipError('depth_bce: pred must be float32, got %s' % pred.dtype)
+        pred = pred.detach().contiguous()
+        if labels.dtype != _i32 or labels.numel() != BN * hw:
+            raise _lib.PreworldHipError('labels must be int32 with %d entries, got %s %s' % (BN * hw, labels.dtype, tuple(labels.shape)))
+        labels = labels.contiguous()
+        ws = _workspace(_lib.call_size('pw_depth_bce_ws_bytes', BN * hw), pred.device)
+        loss = torch.empty((), device=pred.device, dtype=_f32)
+        n_fg = torch.empty(1, device=pred.device, dtype=_i32)
+        _lib.call('pw_depth_bce_fwd', _chk(pred, _f32, 'pred'), _chk(labels, _i32, 'labels'), BN, D, hw, float(weight), _p(ws),
+                  _p(loss), _p(n_fg), _stream())
+        ctx.save_for_backward(pred, labels, n_fg)
+        ctx.weight = float(weight)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        pred, labels, n_fg = ctx.saved_tensors
+        BN, D = pred.shape[:2]
+        grad = torch.empty_like(pred)
+        g = grad_out.detach().float().contiguous().view(1)
+        _lib.call('pw_depth_bce_bwd', _chk(pred, _f32, 'pred'), _chk(labels, _i32, 'labels'), _chk(g, _f32, 'grad_out'),
+                  _chk(n_fg, _i32, 'n_fg'), BN, D, pred[0, 0].numel(), ctx.weight, _p(grad), _stream())
+        return grad, None, None
+
+
+def depth_bce(pred, labels, weight):
+    return DepthBCE.apply(pred, labels, weight)
+
+
 # ------------------------------------------------------------------------------ DepthNet tail
 def depthnet_tail(x, D, C):
     """x (BN, >=D+C, H, W) DepthNet output -> (depth (BN,D,H,W) softmaxed over D,
