@@ -544,6 +544,34 @@ int pw_depth_bce_fwd(const float* pred, const int32_t* labels, int BN, int D, in
 int pw_depth_bce_bwd(const float* pred, const int32_t* labels, const float* grad_out, const int32_t* n_fg, int BN, int D,
                      int64_t hw, float weight, float* grad_pred, void* stream);
 
+/* Camera frames to network input (pw_image_prep.hip): mmdet3d/datasets/pipelines/loading_traj_temporal.py:283-290
+ * img_transform_core (= loading.py:955-962: PIL resize, crop, flip, rotate) and :173-180 mmlabNormalize, for all M frames of a
+ * call.  Integer arithmetic up to the uint8 image, so those bytes are PIL's (Pillow 12.2.0: INTEGRATION.md).
+ *   src      uint8[M][H][W][3], RGB as np.array(PIL image) gives it
+ *   params   int32[M][PW_IMAGE_PREP_NPARAM] IN DEVICE MEMORY, per image:
+ *              0 newW, 1 newH (resize dims)   2 x0, 3 y0 (crop origin in the resized image; may leave it: zero fill)
+ *              4 flip   5 rotated (0: angle == 0)   6..11 a0..a5, PIL's 16.16 fixed-point inverse affine of the rotation
+ *              12 table offset of the horizontal axis (W -> newW), 13 its taps per output (ksize)   14, 15 the same, vertical
+ *   tables   int32[n_table] IN DEVICE MEMORY; an axis table of `out` outputs at offset o: tables[o + 2 i] = first source
+ *            index of output i, tables[o + 2 i + 1] = its tap count (<= ksize), tables[o + 2 out + i ksize + k] = tap k as
+ *            PIL's 22-bit fixed point int.  A pass is clip((2^21 + sum px k) >> 22, 0, 255); horizontal first, rounded to
+ *            uint8, then vertical.  Built on the host in float64 (ops.image_prep_plan); an axis with in == out is the identity.
+ *   rows_max most source rows any PW_IMAGE_PREP_TH-row band of the cropped window needs (sizes the LDS tile; a band that
+ *            needs more is computed from its first rows_max rows only, never out of bounds); 1 <= rows_max <= 224
+ *   any_rot  != 0 iff some image has params[5] != 0; then ws (pw_image_prep_ws_bytes bytes) holds the unrotated uint8 windows
+ *            and a second launch rotates them (nearest, about the centre, fill 0).  any_rot == 0: ONE launch, ws unused.
+ *   out      float[M][3][fH][fW]: out[c] = (float(px[2 - c]) - mean[c]) * stdinv[c] (the reference's to_rgb on RGB input:
+ *            plane 0 is blue);  canvas uint8[M][fH][fW][3] or NULL: the image before normalisation (results['canvas']).
+ *   launches_host  NULL or a host int that receives the number of kernel launches enqueued.
+ * Everything is written by stores (no memset): the call can be captured. */
+#define PW_IMAGE_PREP_NPARAM 16
+#define PW_IMAGE_PREP_TH 32
+#define PW_IMAGE_PREP_TW 64
+size_t pw_image_prep_ws_bytes(int M, int fH, int fW, int any_rot);
+int pw_image_prep(const uint8_t* src, int M, int H, int W, int fH, int fW, const int32_t* params, const int32_t* tables,
+                  int64_t n_table, int rows_max, int any_rot, void* ws, float* out, uint8_t* canvas, int* launches_host,
+                  void* stream);
+
 /* Dense camera views of one attribute grid: ray generation (ray.py:34-45 as pts2ray calls it, :50) fused with the march of
  * pw_render_rays (nerf_head.py:32-55 sample_ray incl. bda, :165-269 render_one_scene -- inner | cumdist_thres mask, trilinear
  * look-ups, Raw2Alpha, both fast_color_thres compactions, transmittance scan with the early stop at T < 1e-3 -- and :331-353

@@ -28,6 +28,8 @@ EXTRA = {
     'pw_stereo.hip': ['-ffp-contract=off'],
     # rounding decides pixels and depth bins; the reference's fused inner products are written out with fmaf
     'pw_depth_sup.hip': ['-ffp-contract=off'],
+    # (px - mean) * stdinv must stay a subtract and a multiply: the float output is pinned bit for bit
+    'pw_image_prep.hip': ['-ffp-contract=off'],
 }
 
 

@@ -1746,3 +1746,166 @@ def occ_fscore_accumulate(table, totals, empty):
     _lib.call('pw_occ_fscore_accumulate', _chk(t, _i64, 'table'), t.shape[0], H, _chk(totals, torch.float64, 'totals'),
               _chk(empty, _i64, 'empty'), _stream())
     return totals
+
+
+# ------------------------------------------------------------------------------ camera frames to network input
+IMAGE_PREP_NPARAM = 16   # PW_IMAGE_PREP_NPARAM
+IMAGE_PREP_TILE = (32, 64)   # PW_IMAGE_PREP_TH, PW_IMAGE_PREP_TW
+_PREC = 22
+
+
+def _bicubic(x):
+    """Keys' cubic with a = -0.5 on an array of float64 offsets, the two polynomial pieces as Pillow writes them"""
+    a = -0.5
+    x = np.abs(x)
+    inner = ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    outer = (((x - 5) * x + 8) * x - 4) * a
+    return np.where(x < 1.0, inner, np.where(x < 2.0, outer, 0.0))
+
+
+@functools.lru_cache(maxsize=1024)
+def image_resize_table(n_in, n_out):
+    """Pillow's 8 bpc bicubic (a = -0.5, antialiased) coefficients of one axis n_in -> n_out, built in float64 in Pillow's
+    operation order (Resample.c precompute_coeffs, normalize_coeffs_8bpc): (bounds (n_out,2) int32 [first source index, taps],
+    coefs (n_out,ksize) int32, 22-bit fixed point).  All outputs at once, tap by tap, so that the weight sum of an output is
+    formed in tap order as the C loop forms it.  n_in == n_out is the identity (PIL skips that pass).  Cached per pair (the
+    released training range reaches about 230 widths and 130 heights); the arrays are shared, hence read-only."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in == n_out:
+        bounds = np.stack([np.arange(n_out), np.ones(n_out, np.int64)], 1).astype(np.int32)
+        coefs = np.full((n_out, 1), 1 << _PREC, np.int32)
+    else:
+        scale = float(n_in) / float(n_out)
+        fs = scale if scale > 1.0 else 1.0
+        support = 2.0 * fs
+        ksize = int(np.ceil(support)) * 2 + 1
+        inv = 1.0 / fs
+        center = (np.arange(n_out) + 0.5) * scale
+        first = np.maximum((center - support + 0.5).astype(np.int64), 0)              # the casts truncate, like C's (int)
+        taps = np.minimum((center + support + 0.5).astype(np.int64), n_in) - first
+        w = np.zeros((n_out, ksize))
+        total = np.zeros(n_out)
+        for k in range(ksize):
+            w[:, k] = np.where(k < taps, _bicubic((k + first - center + 0.5) * inv), 0.0)
+            total = total + w[:, k]
+        has = total != 0.0
+        w[has] = w[has] / total[has][:, None]
+        q = w * float(1 << _PREC)
+        coefs = np.where(w < 0, np.trunc(-0.5 + q), np.trunc(0.5 + q)).astype(np.int32)
+        bounds = np.stack([first, taps], 1).astype(np.int32)
+    bounds.setflags(write=False)
+    coefs.setflags(write=False)
+    return bounds, coefs
+
+
+def image_rotation_fixed(angle, w, h):
+    """The six 16.16 integers a0..a5 of PIL's Image.rotate(angle) on a w x h image (nearest, about the centre, no expand):
+    output (x, y) reads ((a2 + a1 y + a0 x) >> 16, (a5 + a4 y + a3 x) >> 16)."""
+    import math
+    if not abs(angle) < 45:
+        raise _lib.PreworldHipError('image rotation must satisfy |angle| < 45 degrees, got %r' % (angle,))
+    t = -math.radians(angle % 360.0)
+    m0, m1 = round(math.cos(t), 15), round(math.sin(t), 15)
+    m3, m4 = round(-math.sin(t), 15), round(math.cos(t), 15)
+    cx, cy = w / 2.0, h / 2.0
+    m2 = m0 * -cx + m1 * -cy + 0.0 + cx
+    m5 = m3 * -cx + m4 * -cy + 0.0 + cy
+    fix = lambda v: int(math.floor(v * 65536.0 + 0.5))      # noqa: E731
+    return (fix(m0), fix(m1), fix(m2 + m0 * 0.5 + m1 * 0.5), fix(m3), fix(m4), fix(m5 + m3 * 0.5 + m4 * 0.5))
+
+
+class ImagePrepPlan:
+    """What pw_image_prep needs besides the pixels, resident on the device: `tables` (int32), `params` (M, 16) int32, and the
+    host-side numbers of the call.  `host_params` / `host_tables` / `offsets` keep the host copies for inspection."""
+    pass
+
+
+def _image_prep_host(src_hw, input_size, augs):
+    H, W = int(src_hw[0]), int(src_hw[1])
+    fH, fW = int(input_size[0]), int(input_size[1])
+    if H < 1 or W < 1 or fH < 1 or fW < 1 or max(H, W, fH, fW) > 32767:
+        raise _lib.PreworldHipError('image_prep_plan: sizes must be 1 .. 32767, got %r -> %r' % (src_hw, input_size))
+    if len(augs) < 1:
+        raise _lib.PreworldHipError('image_prep_plan: no images')
+    TH = IMAGE_PREP_TILE[0]
+    chunks, offsets, n_table = [], {}, 0
+
+    def table(n_in, n_out):
+        nonlocal n_table
+        key = (n_in, n_out)
+        if key not in offsets:
+            b, c = image_resize_table(n_in, n_out)
+            offsets[key] = (n_table, c.shape[1])
+            chunks.extend([b.reshape(-1), c.reshape(-1)])
+            n_table += b.size + c.size
+        return offsets[key]
+    params = np.zeros((len(augs), IMAGE_PREP_NPARAM), np.int32)
+    rows_max = 1
+    for i, (dims, crop, flip, angle) in enumerate(augs):
+        newW, newH = int(dims[0]), int(dims[1])
+        x0, y0, x1, y1 = [int(v) for v in crop]
+        if newW < 1 or newH < 1 or max(newW, newH) > 32767:
+            raise _lib.PreworldHipError('image_prep_plan: image %d: resize dims %r out of range' % (i, dims))
+        if x1 - x0 != fW or y1 - y0 != fH:
+            raise _lib.PreworldHipError('image_prep_plan: image %d: crop %r is not input_size %r' % (i, crop, (fH, fW)))
+        if max(abs(x0), abs(y0)) > 65535:
+            raise _lib.PreworldHipError('image_prep_plan: image %d: crop origin out of range' % i)
+        angle = float(angle)
+        rot = angle % 360.0 != 0
+        a = image_rotation_fixed(angle, fW, fH) if rot else (65536, 0, 0, 0, 65536, 0)
+        (hoff, hks), (voff, vks) = table(W, newW), table(H, newH)
+        params[i] = (newW, newH, x0, y0, 1 if flip else 0, 1 if rot else 0) + tuple(a) + (hoff, hks, voff, vks)
+        vb = image_resize_table(H, newH)[0].astype(np.int64)
+        oy0 = np.arange(0, fH, TH)                  # the band of source rows each tile row stages in LDS
+        ra, rb = np.maximum(oy0 + y0, 0), np.minimum(np.minimum(oy0 + TH, fH) - 1 + y0, newH - 1)
+        ra, rb = ra[ra <= rb], rb[ra <= rb]
+        if ra.size:
+            rows_max = max(rows_max, int((vb[rb, 0] + vb[rb, 1] - vb[ra, 0]).max()))
+    if rows_max > 224:
+        raise _lib.PreworldHipError('image_prep_plan: a %d-row band of the output needs %d source rows; the kernel stages at most 224 '
+                                    '(down-scaling beyond about 6.5x is not supported)' % (TH, rows_max))
+    return H, W, fH, fW, params, np.concatenate(chunks).astype(np.int32), offsets, rows_max
+
+
+def image_prep_plan(src_hw, input_size, augs, device='cuda'):
+    """Plan of ops.prepare_images for M = len(augs) frames of src_hw = (H, W) going to input_size = (fH, fW).  augs: per image
+    (resize_dims (newW, newH), crop (x0, y0, x1, y1), flip, rotate degrees), the tuple the reference's sample_augmentation
+    returns without its first entry (loading_traj_temporal.py:303-329).  Builds PIL's coefficient tables (cached per axis pair)
+    and the per-image parameters on the host and copies them to the device once; a plan is reused for every call with the same
+    augmentation (the test-time one is a constant)."""
+    H, W, fH, fW, params, tables, offsets, rows_max = _image_prep_host(src_hw, input_size, augs)
+    p = ImagePrepPlan()
+    p.src_hw, p.input_size, p.M, p.rows_max = (H, W), (fH, fW), len(augs), rows_max
+    p.any_rot = bool(params[:, 5].any())
+    p.host_params, p.host_tables, p.offsets = params, tables, offsets
+    p.device = torch.device(device)
+    p.params = torch.from_numpy(params).to(p.device)
+    p.tables = torch.from_numpy(tables).to(p.device)
+    p.ws = _workspace(_lib.call_size('pw_image_prep_ws_bytes', p.M, fH, fW, 1), p.device) if p.any_rot else None
+    p.launches = None
+    return p
+
+
+def prepare_images(src_u8, plan, out=None, canvas=None):
+    """img_transform_core + mmlabNormalize (mmdet3d/datasets/pipelines/loading_traj_temporal.py:283-290, 173-180) for all frames
+    of a call: src_u8 (M,H,W,3) uint8 RGB on the device -> (M,3,fH,fW) float32, plane 0 blue (the reference's to_rgb on RGB
+    input).  canvas: optional (M,fH,fW,3) uint8 that receives the transformed image before normalisation (results['canvas']),
+    bit-equal to PIL's.  No host-to-device copy and no synchronisation happen here; `plan.launches` is the number of kernel
+    launches the call enqueued as the library reports it: 1 when no image is rotated, 2 otherwise."""
+    H, W = plan.src_hw
+    fH, fW = plan.input_size
+    if not isinstance(src_u8, torch.Tensor) or tuple(src_u8.shape) != (plan.M, H, W, 3):
+        raise _lib.PreworldHipError('src_u8 must be a (%d,%d,%d,3) tensor, got %s' % (plan.M, H, W, tuple(getattr(src_u8, 'shape', ()))))
+    if out is None:
+        out = torch.empty(plan.M, 3, fH, fW, device=src_u8.device, dtype=_f32)
+    elif tuple(out.shape) != (plan.M, 3, fH, fW):
+        raise _lib.PreworldHipError('out must be (%d,3,%d,%d)' % (plan.M, fH, fW))
+    if canvas is not None and tuple(canvas.shape) != (plan.M, fH, fW, 3):
+        raise _lib.PreworldHipError('canvas must be (%d,%d,%d,3)' % (plan.M, fH, fW))
+    n = ctypes.c_int(0)
+    _lib.call('pw_image_prep', _chk(src_u8, torch.uint8, 'src_u8'), plan.M, H, W, fH, fW, _chk(plan.params, _i32, 'plan.params'),
+              _chk(plan.tables, _i32, 'plan.tables'), plan.tables.numel(), plan.rows_max, int(plan.any_rot), _p(plan.ws),
+              _chk(out, _f32, 'out'), _chk(canvas, torch.uint8, 'canvas') if canvas is not None else None, ctypes.byref(n),
+              _stream())
+    plan.launches = n.value
+    return out
