@@ -351,7 +351,9 @@ k_forecast_h2(const float* __restrict__ v0, long long n_vox_per_sample, int n_sa
   // TWO voxel tiles per wave and trip (round 4): the kernel is bound by its VALU work -- per hidden tile 16 softplus (two quarter-rate
   // transcendentals each) + 16 splits, ~1 050 issue cycles against 384 of MFMA -- and inside ONE tile everything is a dependent
   // chain MFMA -> softplus -> split -> MFMA.  With two independent tiles in the loop body one tile's softplus / split instructions
-  // issue while the other tile's MFMAs execute.
+  // issue while the other tile's MFMAs execute.  The price is registers: the two-tile loop needs more than 168 (230 allocated under
+  // this launch bound; bounds of 3 and 4 blocks per CU spill 96 and 312 bytes per lane), the 124 of the note above are the one-tile
+  // loop -- more than two waves per SIMD are open to NU = 1 only (profiles/forecast_overlap.md).
   constexpr int NU = 2;
   const long long n_pairs = (n_tiles + NU - 1) / NU;
   for (long long pair = (long long)blockIdx.x * 4 + wave; pair < n_pairs; pair += (long long)gridDim.x * 4) {
