@@ -832,8 +832,11 @@ k_pool_bwd(const float4* __restrict__ out_grad, const float* __restrict__ depth,
   if (active) feat_grad[pf * LPV + sub] = fg;
 }
 
+// tree_lpv > 0: a width k_pool_bwd<tree_lpv> serves, reached only because a pointer is not 16-byte aligned.  The dot product is
+// then summed in that kernel's order -- four channels per lane, then the __shfl_xor butterfly, i.e. a balanced pairwise tree over
+// the tree_lpv partial sums (built here with a binary-counter stack) -- so the result does not depend on where a buffer starts.
 __global__ void __launch_bounds__(256)
-k_pool_bwd_generic(int c, int n_intervals, const float* __restrict__ out_grad,
+k_pool_bwd_generic(int c, int tree_lpv, int n_intervals, const float* __restrict__ out_grad,
                    const float* __restrict__ depth, const float* __restrict__ feat,
                    const int32_t* __restrict__ ranks_depth, const int32_t* __restrict__ ranks_feat,
                    const int32_t* __restrict__ ranks_bev, const int32_t* __restrict__ istart,
@@ -846,7 +849,20 @@ k_pool_bwd_generic(int c, int n_intervals, const float* __restrict__ out_grad,
     const float* og = out_grad + (int64_t)ranks_bev[s + i] * c;
     const float* f = feat + (int64_t)ranks_feat[s + i] * c;
     float g = 0.f;
-    for (int ch = 0; ch < c; ++ch) g = g + og[ch] * f[ch];
+    if (tree_lpv > 0) {
+      float stack[7];                                        // tree_lpv <= 64: at most 6 pending subtrees + the new leaf
+      int top = 0;
+      for (int j = 0; j < tree_lpv; ++j) {
+        const float* a = og + 4 * j;
+        const float* b = f + 4 * j;
+        float p = ((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]) + a[3] * b[3];
+        for (int bit = j; bit & 1; bit >>= 1) p = stack[--top] + p;
+        stack[top++] = p;
+      }
+      g = stack[0];
+    } else {
+      for (int ch = 0; ch < c; ++ch) g = g + og[ch] * f[ch];
+    }
     depth_grad[ranks_depth[s + i]] = g;
   }
   float* fg = feat_grad + (int64_t)ranks_feat[s] * c;
@@ -880,8 +896,9 @@ PW_API int pw_bev_pool_v2_backward(const float* out_grad, float* depth_grad, flo
                                             interval_lengths, n_intervals, depth_grad,
                                             (float4*)feat_grad));
   } else {
+    const int tree_lpv = lpv_supported(c) && c <= 256 ? c / 4 : 0;      // misaligned buffers only: keep k_pool_bwd's sum order
     hipLaunchKernelGGL(k_pool_bwd_generic, dim3((unsigned)pw_cdiv(n_intervals, 256)), dim3(256), 0,
-                       st, c, n_intervals, out_grad, depth, feat, ranks_depth, ranks_feat,
+                       st, c, tree_lpv, n_intervals, out_grad, depth, feat, ranks_depth, ranks_feat,
                        ranks_bev, interval_starts, interval_lengths, depth_grad, feat_grad);
   }
   PW_CHECK_LAUNCH();
