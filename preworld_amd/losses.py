@@ -9,9 +9,9 @@ The scalar algebra on the 104 accumulated sums runs in two one-block kernels (pw
 pw_voxel_loss_coef): no host sync, 2 launches forward and 2 backward."""
 import torch
 
-from . import _lib, ops
+from . import _lib
 
-_NS = 104
+_NS = _lib.PW['PW_VOXEL_LOSS_NSTATS']
 _MAXC = 32
 
 
@@ -19,8 +19,8 @@ def _args(pred, target, camera_mask, class_weights):
     if not pred.is_cuda or pred.dtype != torch.float32 or pred.dim() != 5:
         raise _lib.PreworldHipError('pred must be a float32 device tensor (B, C, X, Y, Z)')
     B, C, X, Y, Z = pred.shape
-    t = target.reshape(B, X, Y, Z).to(torch.uint8).contiguous()
-    cm = camera_mask.reshape(B, X, Y, Z).to(torch.uint8).contiguous() if camera_mask is not None else None
+    t = target.reshape(B, X, Y, Z).to(device=pred.device, dtype=torch.uint8).contiguous()
+    cm = camera_mask.reshape(B, X, Y, Z).to(device=pred.device, dtype=torch.uint8).contiguous() if camera_mask is not None else None
     cw = class_weights.to(device=pred.device, dtype=torch.float32).contiguous() if class_weights is not None else None
     return (B, C, X, Y, Z), t, cm, cw
 
@@ -29,8 +29,8 @@ def _stats(pred, t, cm, cw, dims, ignore_index, empty_idx):
     B, C, X, Y, Z = dims
     stats = torch.zeros(_NS, device=pred.device, dtype=torch.float64)
     sb, sc, sx, sy, sz = pred.stride()
-    _lib.call('pw_voxel_loss_stats', ops._p(pred), ops._p(t), ops._p(cm), ops._p(cw), B, C, X, Y, Z, sb, sc, sx,
-              sy, sz, int(ignore_index), int(empty_idx), ops._p(stats), ops._stream())
+    _lib.call('pw_voxel_loss_stats', _lib.strided(pred), t, cm, cw, B, C, X, Y, Z, sb, sc, sx, sy, sz, int(ignore_index),
+              int(empty_idx), stats, _lib.STREAM)
     return stats
 
 
@@ -40,7 +40,7 @@ class _VoxelLosses(torch.autograd.Function):
         dims, t, cm, cw = _args(pred, target, camera_mask, class_weights)
         s = _stats(pred, t, cm, cw, dims, ignore_index, empty_idx)
         out = torch.empty(3, device=pred.device, dtype=torch.float32)
-        _lib.call('pw_voxel_loss_finish', ops._p(s), dims[1], ops._p(out), ops._stream())
+        _lib.call('pw_voxel_loss_finish', s, dims[1], out, _lib.STREAM)
         ctx.save_for_backward(pred, t, cm if cm is not None else torch.empty(0), cw if cw is not None else torch.empty(0), s)
         ctx.meta = (dims, ignore_index, empty_idx, cm is not None, cw is not None)
         return out[0], out[1], out[2]
@@ -52,12 +52,11 @@ class _VoxelLosses(torch.autograd.Function):
         B, C, X, Y, Z = dims
         gout = torch.stack([g_ce, g_sem, g_geo]).to(torch.float32).contiguous()
         coef = torch.empty(2 * _MAXC + 3, device=pred.device, dtype=torch.float32)
-        _lib.call('pw_voxel_loss_coef', ops._p(s), C, ops._p(gout), ops._p(coef), ops._stream())
+        _lib.call('pw_voxel_loss_coef', s, C, gout, coef, _lib.STREAM)
         grad = torch.empty_strided(pred.shape, pred.stride(), device=pred.device, dtype=pred.dtype)
         sb, sc, sx, sy, sz = pred.stride()
-        _lib.call('pw_voxel_loss_grad', ops._p(pred), ops._p(t), ops._p(cm) if has_cm else None,
-                  ops._p(cw) if has_cw else None, ops._p(coef), B, C, X, Y, Z, sb, sc, sx, sy, sz,
-                  int(ignore_index), int(empty_idx), ops._p(grad), ops._stream())
+        _lib.call('pw_voxel_loss_grad', _lib.strided(pred), t, cm if has_cm else None, cw if has_cw else None, coef, B, C, X, Y, Z,
+                  sb, sc, sx, sy, sz, int(ignore_index), int(empty_idx), _lib.strided(grad), _lib.STREAM)
         return grad, None, None, None, None, None
 
 
@@ -89,10 +88,10 @@ class _FocalLoss(torch.autograd.Function):
         B, C, X, Y, Z = dims
         stats = torch.zeros(2, device=pred.device, dtype=torch.float64)
         sb, sc, sx, sy, sz = pred.stride()
-        _lib.call('pw_focal_loss_stats', ops._p(pred), ops._p(t), ops._p(cm), ops._p(cw), B, C, X, Y, Z, sb, sc, sx, sy,
-                  sz, int(ignore_index), float(gamma), float(alpha), ops._p(stats), ops._stream())
+        _lib.call('pw_focal_loss_stats', _lib.strided(pred), t, cm, cw, B, C, X, Y, Z, sb, sc, sx, sy, sz, int(ignore_index),
+                  float(gamma), float(alpha), stats, _lib.STREAM)
         out = torch.empty(1, device=pred.device, dtype=torch.float32)
-        _lib.call('pw_focal_loss_finish', ops._p(stats), float(loss_weight), ops._p(out), ops._stream())
+        _lib.call('pw_focal_loss_finish', stats, float(loss_weight), out, _lib.STREAM)
         ctx.save_for_backward(pred, t, cm if cm is not None else torch.empty(0), cw if cw is not None else torch.empty(0), stats)
         ctx.meta = (dims, ignore_index, gamma, alpha, loss_weight, cm is not None, cw is not None)
         return out[0]
@@ -105,9 +104,9 @@ class _FocalLoss(torch.autograd.Function):
         gout = g.reshape(1).to(torch.float32).contiguous()
         grad = torch.empty_strided(pred.shape, pred.stride(), device=pred.device, dtype=pred.dtype)
         sb, sc, sx, sy, sz = pred.stride()
-        _lib.call('pw_focal_loss_grad', ops._p(pred), ops._p(t), ops._p(cm) if has_cm else None,
-                  ops._p(cw) if has_cw else None, B, C, X, Y, Z, sb, sc, sx, sy, sz, int(ignore_index), float(gamma),
-                  float(alpha), ops._p(stats), float(loss_weight), ops._p(gout), ops._p(grad), ops._stream())
+        _lib.call('pw_focal_loss_grad', _lib.strided(pred), t, cm if has_cm else None, cw if has_cw else None, B, C, X, Y, Z, sb,
+                  sc, sx, sy, sz, int(ignore_index), float(gamma), float(alpha), stats, float(loss_weight), gout,
+                  _lib.strided(grad), _lib.STREAM)
         return grad, None, None, None, None, None, None, None
 
 
@@ -147,8 +146,8 @@ class _Lovasz(torch.autograd.Function):
         sb, sc, sx, sy, sz = probas.stride()
         if need_grad and dprob.stride() != probas.stride():
             dprob = torch.empty_strided(probas.shape, probas.stride(), device=probas.device, dtype=probas.dtype).zero_()
-        _lib.call('pw_lovasz_softmax', ops._p(probas), ops._p(t), ops._p(cm), B, C, X, Y, Z, sb, sc, sx, sy, sz, ign,
-                  ops._p(ws), nbytes, ops._p(out[0:1]), ops._p(out[1:2]), ops._p(dprob), ops._stream())
+        _lib.call('pw_lovasz_softmax', _lib.strided(probas), t, cm, B, C, X, Y, Z, sb, sc, sx, sy, sz, ign, ws, nbytes, out[0:1],
+                  out[1:2], _lib.strided(dprob) if need_grad else None, _lib.STREAM)
         if need_grad:
             ctx.save_for_backward(dprob, out)
         return out[0]

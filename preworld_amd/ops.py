@@ -15,43 +15,22 @@ from . import _lib
 
 _i32 = torch.int32
 _f32 = torch.float32
-RNG_ROW = 1056       # PW_RNG_ROW of include/preworld_hip.h: int32 per range slot
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _chk(t, dtype, name):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise _lib.PreworldHipError('%s must be a CUDA(HIP) tensor' % name)
-    if t.dtype != dtype:
-        raise _lib.PreworldHipError('%s must be %s, got %s' % (name, dtype, t.dtype))
-    if not t.is_contiguous():
-        raise _lib.PreworldHipError('%s must be contiguous' % name)
-    return _ptr(t)
-
-
-class _Ptr(ctypes.c_void_p):
-    """A device-pointer argument that keeps its tensor alive until the argument list is dropped, i.e. until the kernel has been
-    enqueued.  Round 6: `_chk(x.contiguous(), ...)` on a NON-contiguous x used to pass the address of a temporary that was freed
-    before the call -- the caching allocator handed the same block to the next temporary of the same call and its copy overwrote the
-    first (four camera tensors of a B = 2 batch aliasing one buffer: found by the reference-class B = 2 fixtures).  After the
-    enqueue a reuse is stream-ordered behind the kernel and safe."""
-
-
-def _ptr(t):
-    p = _Ptr(t.data_ptr())
-    p._keep = t
-    return p
-
-
-def _p(t):
-    return _ptr(t) if t is not None else None
+RNG_ROW = _lib.PW['PW_RNG_ROW']       # int32 per range slot
 
 
 def _host3(vals):
     return (ctypes.c_float * 3)(*[float(v) for v in vals])
+
+
+def _slice(t):
+    """a destination / residual that may be a channel slice: its layout was validated by _row_stride / _rows (or against the strides
+    the call passes) and goes to the kernel as a row stride"""
+    return _lib.strided(t) if t is not None else None
+
+
+def _f32_typed(grid):
+    """a contiguous bf16 attribute grid for a `const float* grid` parameter (the kernel is told by its grid_bf16 flag)"""
+    return grid.view(-1).view(_f32) if grid.dtype == torch.bfloat16 else grid
 
 
 def _workspace(nbytes, device):
@@ -70,10 +49,8 @@ def copy_many(dsts, srcs):
             raise _lib.PreworldHipError('copy_many: tensors must be contiguous device tensors of equal shape and dtype')
     if n == 0:
         return
-    S = (ctypes.c_void_p * n)(*[s_.data_ptr() for s_ in srcs])
-    D = (ctypes.c_void_p * n)(*[d.data_ptr() for d in dsts])
     B = (ctypes.c_size_t * n)(*[d.numel() * d.element_size() for d in dsts])
-    _lib.call('pw_copy_many', S, D, B, n, _stream())
+    _lib.call('pw_copy_many', _lib.table(srcs), _lib.table(dsts), B, n, _lib.STREAM)
 
 
 def device_info():
@@ -96,8 +73,7 @@ def lss_camera_matrices(sensor2ego, cam2imgs, post_rots):
     ipr = torch.empty(B, N, 3, 3, device=dev, dtype=_f32)
     comb = torch.empty(B, N, 3, 3, device=dev, dtype=_f32)
     tr = torch.empty(B, N, 3, device=dev, dtype=_f32)
-    _lib.call('pw_lss_camera_matrices', B * N, _chk(s, _f32, 'sensor2ego'), _chk(k, _f32, 'cam2imgs'),
-              _chk(r, _f32, 'post_rots'), _p(ipr), _p(comb), _p(tr), _stream())
+    _lib.call('pw_lss_camera_matrices', B * N, s, k, r, ipr, comb, tr, _lib.STREAM)
     return ipr, comb, tr
 
 
@@ -110,11 +86,8 @@ def lss_voxel_index(frustum, inv_post_rot, post_trans, combine, trans, bda, lowe
     dev = frustum.device
     vox = torch.empty(B * N * D * H * W, device=dev, dtype=_i32)
     coor = torch.empty(B, N, D, H, W, 3, device=dev, dtype=_f32) if return_coor else None
-    _lib.call('pw_lss_voxel_index', B, N, D, H, W, _chk(frustum, _f32, 'frustum'),
-              _chk(inv_post_rot, _f32, 'inv_post_rot'), _chk(post_trans, _f32, 'post_trans'),
-              _chk(combine, _f32, 'combine'), _chk(trans, _f32, 'trans'), _chk(bda, _f32, 'bda'),
-              _host3(lower), _host3(interval), int(grid_size[0]), int(grid_size[1]),
-              int(grid_size[2]), _p(vox), _p(coor), _stream())
+    _lib.call('pw_lss_voxel_index', B, N, D, H, W, frustum, inv_post_rot, post_trans, combine, trans, bda, _host3(lower),
+              _host3(interval), int(grid_size[0]), int(grid_size[1]), int(grid_size[2]), vox, coor, _lib.STREAM)
     return (vox, coor) if return_coor else vox
 
 
@@ -142,8 +115,8 @@ def segment_sort(keys, n_keys, aux_div=0, aux_mod=0, long_threshold=0):
     aux = torch.empty(n, device=dev, dtype=_i32) if aux_div else None
     ll = torch.empty(n // (long_threshold + 1) + 1, device=dev, dtype=_i32) if long_threshold else None
     nl = torch.empty(1, device=dev, dtype=_i32) if long_threshold else None
-    _lib.call('pw_segment_sort', n, n_keys, _chk(keys, _i32, 'keys'), _p(ws), nbytes, _p(seg_start),
-              _p(order), aux_div, aux_mod, _p(aux), long_threshold, _p(ll), _p(nl), _stream())
+    _lib.call('pw_segment_sort', n, n_keys, keys, ws, nbytes, seg_start, order, aux_div, aux_mod, aux, long_threshold, ll, nl,
+              _lib.STREAM)
     return VoxelSort(seg_start, order, aux, ll, nl, n_keys)
 
 
@@ -162,8 +135,7 @@ def lss_ranks(seg_start, order, n_voxels, D, HW):
     st = torch.empty(nmax, device=dev, dtype=_i32)
     ln = torch.empty(nmax, device=dev, dtype=_i32)
     counts = torch.empty(2, device=dev, dtype=_i32)
-    _lib.call('pw_lss_ranks', n_voxels, _p(seg_start), _p(order), D, HW, _p(ws), nbytes, _p(rb),
-              _p(rd), _p(rf), _p(st), _p(ln), _p(counts), _stream())
+    _lib.call('pw_lss_ranks', n_voxels, seg_start, order, D, HW, ws, nbytes, rb, rd, rf, st, ln, counts, _lib.STREAM)
     kept, ni = counts.tolist()
     if kept == 0:
         return None, None, None, None, None
@@ -182,11 +154,8 @@ def bev_pool_dense(depth, feat, vs, out=None, out_h2=False):
     orng = None
     if out_h2:
         out, orng = _out_h2(out, feat.device)
-    _lib.call('pw_bev_pool_dense', _chk(depth, _f32, 'depth'), _chk(feat, _f32, 'feat'),
-              _chk(vs.seg_start, _i32, 'seg_start'), _chk(vs.order, _i32, 'order'),
-              _chk(vs.order_feat, _i32, 'order_feat'), vs.n_keys, C,
-              LONG_SEGMENT if vs.long_list is not None else 0, _p(vs.long_list), _p(vs.n_long),
-              _chk(out, _f32, 'out'), int(bool(out_h2)), _p(orng), _stream())
+    _lib.call('pw_bev_pool_dense', depth, feat, vs.seg_start, vs.order, vs.order_feat, vs.n_keys, C,
+              LONG_SEGMENT if vs.long_list is not None else 0, vs.long_list, vs.n_long, out, int(bool(out_h2)), orng, _lib.STREAM)
     return H2(out, orng) if out_h2 else out
 
 
@@ -210,11 +179,9 @@ def lss_lift_pool(frustum, sensor2ego, cam2imgs, post_rots, post_trans, bda, low
     nbytes = _lib.call_size('pw_lss_lift_pool_workspace_bytes', B * N * D * H * W, n_vox, B * N)
     ws = _workspace(nbytes, dev)
     f = lambda t: t.contiguous().float()
-    _lib.call('pw_lss_lift_pool', B, N, D, H, W, _chk(frustum, _f32, 'frustum'), _chk(f(sensor2ego), _f32, 'sensor2ego'),
-              _chk(f(cam2imgs), _f32, 'cam2imgs'), _chk(f(post_rots), _f32, 'post_rots'), _chk(f(post_trans), _f32, 'post_trans'),
-              _chk(f(bda), _f32, 'bda'), _host3(lower), _host3(interval), int(grid_size[0]), int(grid_size[1]),
-              int(grid_size[2]), _chk(depth, _f32, 'depth'), _chk(feat, _f32, 'feat'), C, _p(ws), nbytes,
-              _chk(out, _f32, 'out'), int(bool(out_h2)), _p(orng), _stream())
+    _lib.call('pw_lss_lift_pool', B, N, D, H, W, frustum, f(sensor2ego), f(cam2imgs), f(post_rots), f(post_trans), f(bda),
+              _host3(lower), _host3(interval), int(grid_size[0]), int(grid_size[1]), int(grid_size[2]), depth, feat, C, ws, nbytes,
+              out, int(bool(out_h2)), orng, _lib.STREAM)
     return H2(out, orng) if out_h2 else out
 
 
@@ -224,24 +191,15 @@ def bev_pool_v2_forward(depth, feat, out, ranks_depth, ranks_feat, ranks_bev, in
     """Same call as bev_pool_v2_ext.bev_pool_v2_forward
     (mmdet3d/ops/bev_pool_v2/src/bev_pool.cpp:30-57): out (B,Z,Y,X,C) pre-zeroed, in/out;
     interval_lengths BEFORE interval_starts."""
-    _lib.call('pw_bev_pool_v2_forward', _chk(depth, _f32, 'depth'), _chk(feat, _f32, 'feat'),
-              _chk(out, _f32, 'out'), _chk(ranks_depth, _i32, 'ranks_depth'),
-              _chk(ranks_feat, _i32, 'ranks_feat'), _chk(ranks_bev, _i32, 'ranks_bev'),
-              _chk(interval_lengths, _i32, 'interval_lengths'),
-              _chk(interval_starts, _i32, 'interval_starts'), feat.shape[-1],
-              interval_lengths.numel(), _stream())
+    _lib.call('pw_bev_pool_v2_forward', depth, feat, out, ranks_depth, ranks_feat, ranks_bev, interval_lengths, interval_starts,
+              feat.shape[-1], interval_lengths.numel(), _lib.STREAM)
 
 
 def bev_pool_v2_backward(out_grad, depth_grad, feat_grad, depth, feat, ranks_depth, ranks_feat,
                          ranks_bev, interval_lengths, interval_starts):
     """Same call as bev_pool_v2_ext.bev_pool_v2_backward (bev_pool.cpp:74-104)."""
-    _lib.call('pw_bev_pool_v2_backward', _chk(out_grad, _f32, 'out_grad'),
-              _chk(depth_grad, _f32, 'depth_grad'), _chk(feat_grad, _f32, 'feat_grad'),
-              _chk(depth, _f32, 'depth'), _chk(feat, _f32, 'feat'),
-              _chk(ranks_depth, _i32, 'ranks_depth'), _chk(ranks_feat, _i32, 'ranks_feat'),
-              _chk(ranks_bev, _i32, 'ranks_bev'), _chk(interval_lengths, _i32, 'interval_lengths'),
-              _chk(interval_starts, _i32, 'interval_starts'), out_grad.shape[-1],
-              interval_lengths.numel(), _stream())
+    _lib.call('pw_bev_pool_v2_backward', out_grad, depth_grad, feat_grad, depth, feat, ranks_depth, ranks_feat, ranks_bev,
+              interval_lengths, interval_starts, out_grad.shape[-1], interval_lengths.numel(), _lib.STREAM)
 
 
 class QuickCumsumCuda(torch.autograd.Function):
@@ -386,9 +344,8 @@ def conv3d_ndhwc(x, wpk, scale=None, bias=None, residual=None, cout0=None, cout1
         raise _lib.PreworldHipError('bias must have cout_total=%d entries' % cout_total)
     if nch * 32 != Cin or taps != ksize ** 3:
         raise _lib.PreworldHipError('packed weight does not match Cin/ksize')
-    _lib.call('pw_conv3d_ndhwc', _chk(x, _f32, 'x'), _chk(wpk, _f32, 'wpk'), _p(scale), _p(bias),
-              _p(residual), _p(y0), _p(y1), B, D, H, W, Cin, cout_total, cout0, cout1, ld0, ld1,
-              ksize, stride, int(relu0), int(relu1), algo, _stream())
+    _lib.call('pw_conv3d_ndhwc', x, wpk, scale, bias, _slice(residual), _slice(y0), _slice(y1), B, D, H, W, Cin, cout_total, cout0,
+              cout1, ld0, ld1, ksize, stride, int(relu0), int(relu1), algo, _lib.STREAM)
     return (y0, y1) if cout1 else y0
 
 
@@ -442,8 +399,8 @@ def conv3d_wino(x, uwpk, scale=None, bias=None, residual=None, cout0=None, cout1
         raise _lib.PreworldHipError('scale must have cout_total=%d entries' % cout_total)
     if bias is not None and bias.numel() != cout_total:
         raise _lib.PreworldHipError('bias must have cout_total=%d entries' % cout_total)
-    _lib.call('pw_conv3d_wino', _chk(x, _f32, 'x'), _chk(uwpk, _f32, 'uwpk'), _p(scale), _p(bias), _p(residual),
-              _p(y0), _p(y1), B, D, H, W, Cin, cout_total, cout0, cout1, ld0, ld1, int(relu0), int(relu1), _stream())
+    _lib.call('pw_conv3d_wino', x, uwpk, scale, bias, _slice(residual), _slice(y0), _slice(y1), B, D, H, W, Cin, cout_total, cout0,
+              cout1, ld0, ld1, int(relu0), int(relu1), _lib.STREAM)
     return (y0, y1) if cout1 else y0
 
 
@@ -479,12 +436,12 @@ class RangeCtx:
 
     def fold(self):
         """end of a pass: fold the partial maxima the kernels raised into the slots and refresh `compact` (one small launch)"""
-        _lib.call('pw_rng_fold', _p(self.tab), self.tab.shape[0], _p(self.compact), _stream())
+        _lib.call('pw_rng_fold', self.tab, self.tab.shape[0], self.compact, _lib.STREAM)
 
     def audit(self):
         """after fold(): the hard-window test of check() on the device, accumulated in `sticky` (pw_rng_audit) -- capturable, so
         every replay of a graph is tested without the host waiting for it; read the verdict with audited()"""
-        _lib.call('pw_rng_audit', _p(self.compact), self.compact.shape[0], _p(self.sticky), _stream())
+        _lib.call('pw_rng_audit', self.compact, self.compact.shape[0], self.sticky, _lib.STREAM)
 
     def audited(self):
         """(passes that left their calibrated ranges, passes audited) since the table was created (synchronises)"""
@@ -572,7 +529,7 @@ def new_slot(device):
 
 def slot_state(slot):
     """(exponent, largest recorded |value|) of one range slot as host numbers (folds its partial maxima first; syncs)"""
-    _lib.call('pw_rng_fold', _p(slot), 1, None, _stream())
+    _lib.call('pw_rng_fold', slot, 1, None, _lib.STREAM)
     e, bits = slot[:2].tolist()
     import struct
     return e, struct.unpack('f', struct.pack('i', bits))[0]
@@ -627,8 +584,8 @@ class H2:
 
 
 def _rng(h):
-    """ctypes pointer of an H2's range slot (NULL without one)"""
-    return _p(h.rng) if isinstance(h, H2) and h.rng is not None else None
+    """an H2's range slot (None -> NULL without one)"""
+    return h.rng if isinstance(h, H2) and h.rng is not None else None
 
 
 def _out_h2(o, device):
@@ -675,7 +632,7 @@ def f32_to_h2(x, out=None):
             buf = torch.empty(x.shape, device=x.device, dtype=_f32)
         slot, auto = torch.zeros(RNG_ROW, dtype=_i32, device=x.device), 1
     _, _, ldy = _rows(buf, 'out')
-    _lib.call('pw_f32_to_h2', _p(x), _p(buf), n, C, ldx, ldy, _p(slot), auto, _stream())
+    _lib.call('pw_f32_to_h2', _slice(x), _slice(buf), n, C, ldx, ldy, slot, auto, _lib.STREAM)
     return H2(buf, slot)
 
 
@@ -685,7 +642,7 @@ def h2_to_f32(x, out=None):
     if out is None:
         out = torch.empty(x.shape, device=x.buf.device, dtype=_f32)
     _, _, ldy = _rows(out, 'out')
-    _lib.call('pw_h2_to_f32', _p(x.buf), _p(out), n, C, ldx, ldy, _rng(x), _stream())
+    _lib.call('pw_h2_to_f32', _slice(x.buf), _slice(out), n, C, ldx, ldy, _rng(x), _lib.STREAM)
     return out
 
 
@@ -766,12 +723,9 @@ def conv3d_h2(x, wpk, scale, bias=None, residual=None, cout0=None, cout1=0, relu
         raise _lib.PreworldHipError('conv3d_h2 needs scale = (BN scale or 1) * inv_scale of pack_conv_weight_h2')
     if scale.numel() != cout_total or (bias is not None and bias.numel() != cout_total):
         raise _lib.PreworldHipError('scale (with the weight pre-scale folded in) / bias must have cout_total=%d entries' % cout_total)
-    xb = x.buf
-    if not xb.is_contiguous():
-        raise _lib.PreworldHipError('x must be dense')
-    _lib.call('pw_conv3d_h2', _p(xb), _chk(wpk, _f32, 'wpk'), _p(scale), _p(bias), _p(res), _p(y0), _p(y1), B, Din, Hin, Win,
-              Cin, cout_total, cout0, cout1, ld0, ld1, ksize, stride, int(relu0), int(relu1), algo, fm0, fm1, fmr,
-              _rng(x), _rng(residual), _p(rng0), _p(rng1), _stream())
+    _lib.call('pw_conv3d_h2', x.buf, wpk, scale, bias, _slice(res), _slice(y0), _slice(y1), B, Din, Hin, Win, Cin, cout_total,
+              cout0, cout1, ld0, ld1, ksize, stride, int(relu0), int(relu1), algo, fm0, fm1, fmr, _rng(x), _rng(residual), rng0,
+              rng1, _lib.STREAM)
     r0 = H2(y0, rng0) if fm0 else y0
     if cout1:
         return r0, (H2(y1, rng1) if fm1 else y1)
@@ -789,10 +743,8 @@ def fpn3d_fuse(x8, wpk8, y16, y32, scale, bias, relu=True, out=None, out_h2=Fals
     orng = None
     if out_h2:
         out, orng = _out_h2(out, xb.device)
-    _lib.call('pw_fpn3d_fuse', _chk(xb, _f32, 'x8'), _chk(wpk8, _f32, 'wpk8'), _chk(y16, _f32, 'y16'),
-              _chk(y32, _f32, 'y32'), _p(scale), _p(bias), _chk(out, _f32, 'out'), B, D, H, W, C8,
-              y16.shape[1], y16.shape[2], y16.shape[3], y32.shape[1], y32.shape[2], y32.shape[3],
-              int(relu), int(x_h2), int(bool(out_h2)), _rng(x8), _p(orng), _stream())
+    _lib.call('pw_fpn3d_fuse', xb, wpk8, y16, y32, scale, bias, out, B, D, H, W, C8, y16.shape[1], y16.shape[2], y16.shape[3],
+              y32.shape[1], y32.shape[2], y32.shape[3], int(relu), int(x_h2), int(bool(out_h2)), _rng(x8), orng, _lib.STREAM)
     return H2(out, orng) if out_h2 else out
 
 
@@ -818,10 +770,8 @@ def occ_head_fused(x, wpk, scale, bias, w1, s1, b1, w2, want_logits=False, occ=N
         occ = torch.empty(B, D, H, W, device=x.device, dtype=torch.uint8)
     logits = torch.empty(B, D, H, W, 18, device=x.device, dtype=_f32) if want_logits else None
     geo = torch.empty(B, D, H, W, device=x.device, dtype=torch.uint8) if want_geo else None
-    _lib.call('pw_occ_head_fused', _chk(x, _f32, 'x'), _chk(wpk, _f32, 'wpk'), _chk(scale, _f32, 'scale'),
-              _chk(bias, _f32, 'bias'), _chk(w1, _f32, 'w1'), _chk(s1, _f32, 's1'), _chk(b1, _f32, 'b1'),
-              _chk(w2, _f32, 'w2'), _p(occ), _p(logits), _p(geo), int(empty_idx), B, D, H, W, Cin, 16, 8, 18,
-              64 if wpk.dim() == 5 else (16 if wpk.shape[-1] == 8 else 32), _stream())
+    _lib.call('pw_occ_head_fused', x, wpk, scale, bias, w1, s1, b1, w2, occ, logits, geo, int(empty_idx), B, D, H, W, Cin, 16, 8,
+              18, 64 if wpk.dim() == 5 else (16 if wpk.shape[-1] == 8 else 32), _lib.STREAM)
     out = (occ,) + ((logits,) if want_logits else ()) + ((geo,) if want_geo else ())
     return out if len(out) > 1 else occ
 
@@ -905,10 +855,9 @@ def occ_head_h2(x, wpk, scale, bias, tailpk, inv2, bounds, want_logits=False, oc
         strides = (ctypes.c_int64 * 4)(*st)
         span = 1 + sum((n - 1) * v for n, v in zip((B, D, H, W), st))
         # (the C side rejects overlapping stride sets -- two voxels storing to one byte would race)
-    _lib.call('pw_occ_head_h2_strided', _chk(x.buf, _f32, 'x'), _chk(wpk, _f32, 'wpk'), _chk(scale, _f32, 'scale'),
-              _chk(bias, _f32, 'bias'), _chk(tailpk, _f32, 'tailpk'), float(inv2), _p(occ), _p(logits), _p(geo), strides, int(span),
-              int(empty_idx), B, D, H, W, Cin, 16, 8, 18, _rng(x), float(bounds[0]), float(bounds[1]), float(bounds[2]),
-              float(bounds[3]), _stream())
+    _lib.call('pw_occ_head_h2_strided', x.buf, wpk, scale, bias, tailpk, float(inv2), _slice(occ), logits, _slice(geo), strides,
+              int(span), int(empty_idx), B, D, H, W, Cin, 16, 8, 18, _rng(x), float(bounds[0]), float(bounds[1]), float(bounds[2]),
+              float(bounds[3]), _lib.STREAM)
     out = (occ,) + ((logits,) if want_logits else ()) + ((geo,) if want_geo else ())
     return out if len(out) > 1 else occ
 
@@ -916,8 +865,7 @@ def occ_head_h2(x, wpk, scale, bias, tailpk, inv2, bounds, want_logits=False, oc
 def forecast_pack(fusion_w1, fusion_w2):
     w1p = torch.empty(4096, device=fusion_w1.device, dtype=_f32)
     w2p = torch.empty(4096, device=fusion_w1.device, dtype=_f32)
-    _lib.call('pw_forecast_pack', _chk(fusion_w1, _f32, 'fusion_head.0.weight'),
-              _chk(fusion_w2, _f32, 'fusion_head.2.weight'), _p(w1p), _p(w2p), _stream())
+    _lib.call('pw_forecast_pack', fusion_w1, fusion_w2, w1p, w2p, _lib.STREAM)
     return w1p, w2p
 
 
@@ -929,10 +877,7 @@ def forecast_prologue(ego, plan, fusion_w1, fusion_b1):
     c1 = torch.empty(n, 128, device=ego.device, dtype=_f32)
     c1p = torch.empty(n, 128, device=ego.device, dtype=_f32)
     (w0, b0), (w2, b2), (w4, b4) = plan
-    _lib.call('pw_forecast_prologue', _chk(ego, _f32, 'ego'), n, dim, _chk(w0, _f32, 'w0'),
-              _chk(b0, _f32, 'b0'), _chk(w2, _f32, 'w2'), _chk(b2, _f32, 'b2'), _chk(w4, _f32, 'w4'),
-              _chk(b4, _f32, 'b4'), _chk(fusion_w1, _f32, 'fw1'), _chk(fusion_b1, _f32, 'fb1'),
-              _p(ef), _p(c1), _p(c1p), _stream())
+    _lib.call('pw_forecast_prologue', ego, n, dim, w0, b0, w2, b2, w4, b4, fusion_w1, fusion_b1, ef, c1, c1p, _lib.STREAM)
     return ef, c1, c1p
 
 
@@ -941,9 +886,7 @@ def forecast_steps(v0, n_samples, w1p, w2p, c1p, fusion_b2, n_steps, states=None
     n_total = v0.numel() // 32
     if states is None:
         states = torch.empty((n_steps,) + tuple(v0.shape), device=v0.device, dtype=_f32)
-    _lib.call('pw_forecast_steps', _chk(v0, _f32, 'v0'), n_total // n_samples, n_samples,
-              _chk(w1p, _f32, 'w1p'), _chk(w2p, _f32, 'w2p'), _chk(c1p, _f32, 'c1p'),
-              _chk(fusion_b2, _f32, 'fb2'), n_steps, _chk(states, _f32, 'states'), _stream())
+    _lib.call('pw_forecast_steps', v0, n_total // n_samples, n_samples, w1p, w2p, c1p, fusion_b2, n_steps, states, _lib.STREAM)
     return states
 
 
@@ -993,15 +936,14 @@ def forecast_steps_h2(v0, n_samples, packed, c1p, fusion_b2, n_steps, states=Non
     states, srng = _out_h2(states, vbuf.device)
     if srng is None:
         srng = new_slot(vbuf.device)
-    _lib.call('pw_forecast_steps_h2', _chk(vbuf, _f32, 'v0'), n_total // n_samples, n_samples, _chk(w1p, _f32, 'w1p'),
-              _chk(w2p, _f32, 'w2p'), float(inv1), float(inv2), _chk(c1p, _f32, 'c1p'), _chk(fusion_b2, _f32, 'fb2'),
-              n_steps, _chk(states, _f32, 'states'), int(v0_h2), int(bool(out_h2)), _rng(v0), _p(srng), float(l1), _stream())
+    _lib.call('pw_forecast_steps_h2', vbuf, n_total // n_samples, n_samples, w1p, w2p, float(inv1), float(inv2), c1p, fusion_b2,
+              n_steps, states, int(v0_h2), int(bool(out_h2)), _rng(v0), srng, float(l1), _lib.STREAM)
     return H2(states, srng) if out_h2 else states
 
 
 def softplus(x):
     y = torch.empty_like(x)
-    _lib.call('pw_softplus', _chk(x, _f32, 'x'), _p(y), x.numel(), _stream())
+    _lib.call('pw_softplus', x, y, x.numel(), _lib.STREAM)
     return y
 
 
@@ -1011,19 +953,15 @@ def pts2ray(coor, label_depth, label_seg, label_img, c2w, cam_intrinsic):
     {x, y, depth, seg, rays_o[3], rays_d[3], viewdirs[3], rgb[3]}."""
     n = coor.shape[0]
     rays = torch.empty(n, 16, device=coor.device, dtype=_f32)
-    _lib.call('pw_pts2ray', _chk(coor.float().contiguous(), _f32, 'coor'),
-              _chk(label_depth.float().contiguous(), _f32, 'label_depth'),
-              _chk(label_seg.float().contiguous(), _f32, 'label_seg'),
-              _chk(label_img.float().contiguous(), _f32, 'label_img'),
-              _chk(c2w.float().contiguous(), _f32, 'c2w'), _chk(cam_intrinsic.float().contiguous(), _f32, 'K'),
-              n, _p(rays), _stream())
+    _lib.call('pw_pts2ray', coor.float().contiguous(), label_depth.float().contiguous(), label_seg.float().contiguous(),
+              label_img.float().contiguous(), c2w.float().contiguous(), cam_intrinsic.float().contiguous(), n, rays, _lib.STREAM)
     return rays
 
 
 def class_count(rays, n_cls=17, counts=None):
     if counts is None:
         counts = torch.zeros(n_cls, device=rays.device, dtype=torch.int64)
-    _lib.call('pw_class_count', _chk(rays, _f32, 'rays'), rays.shape[0], n_cls, _p(counts), _stream())
+    _lib.call('pw_class_count', rays, rays.shape[0], n_cls, counts, _lib.STREAM)
     return counts
 
 
@@ -1032,9 +970,8 @@ def wrs_weights(rays, frame_id, balance_weight, dynamic_class, weight_adj=0.3, w
     n = rays.shape[0]
     w = torch.empty(n, device=rays.device, dtype=_f32)
     dyn = dynamic_class.to(device=rays.device, dtype=_i32).contiguous()
-    _lib.call('pw_wrs_weights', _chk(rays, _f32, 'rays'), n, int(frame_id),
-              _chk(balance_weight.float().contiguous(), _f32, 'balance_weight'), balance_weight.numel(),
-              _p(dyn), dyn.numel(), float(weight_adj), float(weight_dyn), _p(w), _stream())
+    _lib.call('pw_wrs_weights', rays, n, int(frame_id), balance_weight.float().contiguous(), balance_weight.numel(), dyn,
+              dyn.numel(), float(weight_adj), float(weight_dyn), w, _lib.STREAM)
     return w
 
 
@@ -1071,10 +1008,8 @@ def lidar_depth_maps(points, lidar2img, post_rots, post_trans, image_hw, depth_r
     pts, offsets, B, N, l2i, pr, pt = _sweep_args(points, offsets, lidar2img, post_rots, post_trans)
     H, W = int(image_hw[0]), int(image_hw[1])
     out = torch.empty(B, N, H // downsample, W // downsample, device=pts.device, dtype=_f32)
-    _lib.call('pw_lidar_depth_maps', _chk(pts, _f32, 'points'), pts.shape[0], pts.shape[1],
-              _chk(offsets, _i32, 'offsets') if offsets is not None else None, B, N, _chk(l2i, _f32, 'lidar2img'),
-              _chk(pr, _f32, 'post_rots'), _chk(pt, _f32, 'post_trans'), H, W, int(downsample), float(depth_range[0]),
-              float(depth_range[1]), _p(out), _stream())
+    _lib.call('pw_lidar_depth_maps', pts, pts.shape[0], pts.shape[1], offsets, B, N, l2i, pr, pt, H, W, int(downsample),
+              float(depth_range[0]), float(depth_range[1]), out, _lib.STREAM)
     return out
 
 
@@ -1089,10 +1024,8 @@ def lidar_depth_labels(points, lidar2img, post_rots, post_trans, image_hw, depth
     D = int(D) if D is not None else int(round((d1 - d0) / dstep))
     ld = int(loss_downsample)
     out = torch.empty(B * N, H // downsample // ld, W // downsample // ld, device=pts.device, dtype=_i32)
-    _lib.call('pw_lidar_depth_labels', _chk(pts, _f32, 'points'), pts.shape[0], pts.shape[1],
-              _chk(offsets, _i32, 'offsets') if offsets is not None else None, B, N, _chk(l2i, _f32, 'lidar2img'),
-              _chk(pr, _f32, 'post_rots'), _chk(pt, _f32, 'post_trans'), H, W, int(downsample), ld, d0, d1, dstep, D, _p(out),
-              _stream())
+    _lib.call('pw_lidar_depth_labels', pts, pts.shape[0], pts.shape[1], offsets, B, N, l2i, pr, pt, H, W, int(downsample), ld, d0,
+              d1, dstep, D, out, _lib.STREAM)
     return out
 
 
@@ -1106,7 +1039,7 @@ def depth_map_labels(gt_depth, downsample, depth_cfg, D=None):
     d0, d1, dstep = [float(v) for v in depth_cfg]
     D = int(D) if D is not None else int(round((d1 - d0) / dstep))
     out = torch.empty(V, H // downsample, W // downsample, device=g.device, dtype=_i32)
-    _lib.call('pw_depth_map_labels', _chk(g, _f32, 'gt_depth'), V, H, W, int(downsample), d0, dstep, D, _p(out), _stream())
+    _lib.call('pw_depth_map_labels', g, V, H, W, int(downsample), d0, dstep, D, out, _lib.STREAM)
     return out
 
 
@@ -1128,8 +1061,7 @@ class DepthBCE(torch.autograd.Function):
         ws = _workspace(_lib.call_size('pw_depth_bce_ws_bytes', BN * hw), pred.device)
         loss = torch.empty((), device=pred.device, dtype=_f32)
         n_fg = torch.empty(1, device=pred.device, dtype=_i32)
-        _lib.call('pw_depth_bce_fwd', _chk(pred, _f32, 'pred'), _chk(labels, _i32, 'labels'), BN, D, hw, float(weight), _p(ws),
-                  _p(loss), _p(n_fg), _stream())
+        _lib.call('pw_depth_bce_fwd', pred, labels, BN, D, hw, float(weight), ws, loss, n_fg, _lib.STREAM)
         ctx.save_for_backward(pred, labels, n_fg)
         ctx.weight = float(weight)
         return loss
@@ -1140,8 +1072,7 @@ class DepthBCE(torch.autograd.Function):
         BN, D = pred.shape[:2]
         grad = torch.empty_like(pred)
         g = grad_out.detach().float().contiguous().view(1)
-        _lib.call('pw_depth_bce_bwd', _chk(pred, _f32, 'pred'), _chk(labels, _i32, 'labels'), _chk(g, _f32, 'grad_out'),
-                  _chk(n_fg, _i32, 'n_fg'), BN, D, pred[0, 0].numel(), ctx.weight, _p(grad), _stream())
+        _lib.call('pw_depth_bce_bwd', pred, labels, g, n_fg, BN, D, pred[0, 0].numel(), ctx.weight, grad, _lib.STREAM)
         return grad, None, None
 
 
@@ -1156,7 +1087,7 @@ def depthnet_tail(x, D, C):
     BN, XC, H, W = x.shape
     depth = torch.empty(BN, D, H, W, device=x.device, dtype=_f32)
     feat = torch.empty(BN, H, W, C, device=x.device, dtype=_f32)
-    _lib.call('pw_depthnet_tail', _chk(x, _f32, 'x'), BN, XC, D, C, H * W, _p(depth), _p(feat), _stream())
+    _lib.call('pw_depthnet_tail', x, BN, XC, D, C, H * W, depth, feat, _lib.STREAM)
     return depth, feat
 
 
@@ -1177,11 +1108,9 @@ def stereo_cost_volume(prev, curr, frustum, k2s_sensor, intrins, post_rots, post
     ipr, comb, tr = lss_camera_matrices(k2s_sensor, intrins, post_rots)
     out = torch.empty(BN, D, H, W, device=dev, dtype=_f32)
     sbn, sc, sy, sx = curr.stride()
-    _lib.call('pw_stereo_cost_volume', _p(prev), _p(curr), BN, C, H, W, sbn, sc, sy, sx, _p(ds), D, _p(xs), _p(ys),
-              _p(ipr), _chk(post_trans.reshape(BN, 3).float().contiguous(), _f32, 'post_trans'), _p(comb), _p(tr),
-              _chk(intrins.reshape(BN, 9).float().contiguous(), _f32, 'intrins'),
-              _chk(post_rots.reshape(BN, 9).float().contiguous(), _f32, 'post_rots'),
-              float(4 * W), float(4 * H), float(bias), _p(out), _stream())
+    _lib.call('pw_stereo_cost_volume', _lib.strided(prev), _lib.strided(curr), BN, C, H, W, sbn, sc, sy, sx, ds, D, xs, ys, ipr,
+              post_trans.reshape(BN, 3).float().contiguous(), comb, tr, intrins.reshape(BN, 9).float().contiguous(),
+              post_rots.reshape(BN, 9).float().contiguous(), float(4 * W), float(4 * H), float(bias), out, _lib.STREAM)
     return out
 
 
@@ -1192,7 +1121,7 @@ def global_avgpool_ndhwc(x):
     B, C = x.shape[0], x.shape[-1]
     n_vox = x.numel() // (B * C)
     y = torch.empty(B, C, device=x.device, dtype=_f32)
-    _lib.call('pw_global_avgpool_ndhwc', _chk(x, _f32, 'x'), B, n_vox, C, _p(y), _stream())
+    _lib.call('pw_global_avgpool_ndhwc', x, B, n_vox, C, y, _lib.STREAM)
     return y
 
 
@@ -1204,9 +1133,8 @@ def linear_act(x, weight, bias=None, act=None):
     rows, n_in = x.shape
     n_out = weight.shape[0]
     y = torch.empty(rows, n_out, device=x.device, dtype=_f32)
-    _lib.call('pw_linear_act', _chk(x, _f32, 'x'), _chk(weight, _f32, 'weight'),
-              _p(bias.contiguous()) if bias is not None else None, _p(y), rows, n_in, n_out, _ACT[act],
-              _stream())
+    _lib.call('pw_linear_act', x, weight, bias.contiguous() if bias is not None else None, y, rows, n_in, n_out, _ACT[act],
+              _lib.STREAM)
     return y
 
 
@@ -1270,9 +1198,7 @@ def attr_mlp(v_cl, packed, final_softplus=True, out=None):
     n = v_cl.numel() // 32
     if out is None:
         out = torch.empty(tuple(v_cl.shape[:-1]) + (24,), device=v_cl.device, dtype=_f32)
-    _lib.call('pw_attr_mlp', _chk(v_cl, _f32, 'v'), n, _chk(w1p, _f32, 'w1p'), _chk(w2p, _f32, 'w2p'),
-              _chk(b1p, _f32, 'b1p'), _chk(b2, _f32, 'b2'), int(final_softplus), _chk(out, _f32, 'out'),
-              _stream())
+    _lib.call('pw_attr_mlp', v_cl, n, w1p, w2p, b1p, b2, int(final_softplus), out, _lib.STREAM)
     return out
 
 
@@ -1285,15 +1211,13 @@ def raw2alpha(density, shift, interval):
     d = density.contiguous()
     e = torch.empty_like(d)
     a = torch.empty_like(d)
-    _lib.call('pw_raw2alpha', _chk(d, _f32, 'density'), float(shift), float(interval), d.numel(),
-              _p(e), _p(a), _stream())
+    _lib.call('pw_raw2alpha', d, float(shift), float(interval), d.numel(), e, a, _lib.STREAM)
     return e, a
 
 
 def raw2alpha_backward(exp, grad_back, interval):
     g = torch.empty_like(exp)
-    _lib.call('pw_raw2alpha_backward', _chk(exp, _f32, 'exp'), _chk(grad_back.contiguous(), _f32, 'grad_back'),
-              float(interval), exp.numel(), _p(g), _stream())
+    _lib.call('pw_raw2alpha_backward', exp, grad_back.contiguous(), float(interval), exp.numel(), g, _lib.STREAM)
     return g
 
 
@@ -1308,18 +1232,15 @@ def alpha2weight(alpha, ray_id, n_rays):
     last = torch.empty(n_rays, device=dev, dtype=_f32)
     i_s = torch.empty(n_rays, device=dev, dtype=_i64)
     i_e = torch.empty(n_rays, device=dev, dtype=_i64)
-    _lib.call('pw_alpha2weight', _chk(a, _f32, 'alpha'), _chk(ray_id.contiguous(), _i64, 'ray_id'), n,
-              int(n_rays), _p(w), _p(T), _p(last), _p(i_s), _p(i_e), _stream())
+    _lib.call('pw_alpha2weight', a, ray_id.contiguous(), n, int(n_rays), w, T, last, i_s, i_e, _lib.STREAM)
     return w, T, last, i_s, i_e
 
 
 def alpha2weight_backward(alpha, weight, T, alphainv_last, i_start, i_end, n_rays, grad_weights,
                           grad_last):
     g = torch.empty_like(alpha)
-    _lib.call('pw_alpha2weight_backward', _chk(alpha, _f32, 'alpha'), _chk(weight, _f32, 'weight'),
-              _chk(T, _f32, 'T'), _chk(alphainv_last, _f32, 'alphainv_last'), _chk(i_start, _i64, 'i_start'),
-              _chk(i_end, _i64, 'i_end'), int(n_rays), _chk(grad_weights.contiguous(), _f32, 'grad_weights'),
-              _chk(grad_last.contiguous(), _f32, 'grad_last'), alpha.numel(), _p(g), _stream())
+    _lib.call('pw_alpha2weight_backward', alpha, weight, T, alphainv_last, i_start, i_end, int(n_rays), grad_weights.contiguous(),
+              grad_last.contiguous(), alpha.numel(), g, _lib.STREAM)
     return g
 
 
@@ -1328,7 +1249,7 @@ def cumdist_thres(dist, thres):
     d = dist.contiguous()
     R, S = d.shape
     m = torch.empty(R, S, device=d.device, dtype=torch.uint8)
-    _lib.call('pw_cumdist_thres', _chk(d, _f32, 'dist'), float(thres), R, S, _p(m), _stream())
+    _lib.call('pw_cumdist_thres', d, float(thres), R, S, m, _lib.STREAM)
     return m.bool()
 
 
@@ -1392,10 +1313,8 @@ def render_rays(rays_o, rays_d, t, grid, consts, c_sigma=0, c_sem=2, n_sem=17, c
     weights = torch.empty(R, S, device=dev, dtype=_f32) if want_debug else None
     mask = torch.empty(R, S, device=dev, dtype=torch.uint8) if want_debug else None
     ch = (ctypes.c_float * 27)(*[float(v) for v in consts])
-    _lib.call('pw_render_rays', _chk(rays_o.contiguous(), _f32, 'rays_o'),
-              _chk(rays_d.contiguous(), _f32, 'rays_d'), R, _chk(t, _f32, 't'), S,
-              _p(grid), X, Y, Z, GC, c_sigma, c_sem, n_sem, c_rgb, ch, _p(depth),
-              _p(sem), _p(rgb), _p(last), _p(counts), _p(weights), _p(mask), int(bf16), _stream())
+    _lib.call('pw_render_rays', rays_o.contiguous(), rays_d.contiguous(), R, t, S, _f32_typed(grid), X, Y, Z, GC, c_sigma, c_sem,
+              n_sem, c_rgb, ch, depth, sem, rgb, last, counts, weights, mask, int(bf16), _lib.STREAM)
     out = dict(depth=depth, semantic=sem, color=rgb, alphainv_last=last)
     if want_debug:
         out.update(counts=counts, weights=weights, mask=mask.bool())
@@ -1420,8 +1339,7 @@ def _view_args(who, first, K, c2w, hw, outputs, allowed, palette):
     if 'rgb8' in outputs:
         if palette is None:
             raise _lib.PreworldHipError('%s: output rgb8 needs a palette' % who)
-        _chk(palette, torch.uint8, 'palette')
-        if palette.dim() != 2 or palette.shape[1] != 3:
+        if palette.dtype != torch.uint8 or palette.dim() != 2 or palette.shape[1] != 3:
             raise _lib.PreworldHipError('%s: palette must be (n, 3) uint8' % who)
     V, (H, W) = K.shape[0], hw
     out = {o: torch.empty((V, int(H), int(W)) + _VIEW_OUTPUTS[o][1], device=first.device, dtype=_VIEW_OUTPUTS[o][0]) for o in outputs}
@@ -1448,10 +1366,9 @@ def render_views(grid, K, c2w, hw, consts, t, stride=1, origin=(0, 0), outputs=(
     V, H, W, out = _view_args('render_views', grid, K, c2w, hw, outputs, tuple(_VIEW_OUTPUTS), palette)
     Z, Y, X, GC = grid.shape
     ch = (ctypes.c_float * 27)(*[float(v) for v in consts])
-    _lib.call('pw_render_views', _chk(K, _f32, 'K'), _chk(c2w, _f32, 'c2w'), V, H, W, int(origin[0]), int(origin[1]), int(stride),
-              _chk(t, _f32, 't'), t.numel(), _p(grid), X, Y, Z, GC, c_sigma, c_sem, n_sem, c_rgb, ch, _p(out.get('depth')),
-              _p(out.get('cls')), _p(out.get('sem')), _p(out.get('color')), _p(out.get('alphainv_last')), _p(out.get('rgb8')),
-              _p(palette), float(min_opacity), int(bf16), _stream())
+    _lib.call('pw_render_views', K, c2w, V, H, W, int(origin[0]), int(origin[1]), int(stride), t, t.numel(), _f32_typed(grid), X, Y,
+              Z, GC, c_sigma, c_sem, n_sem, c_rgb, ch, out.get('depth'), out.get('cls'), out.get('sem'), out.get('color'),
+              out.get('alphainv_last'), out.get('rgb8'), palette, float(min_opacity), int(bf16), _lib.STREAM)
     return out
 
 
@@ -1472,10 +1389,9 @@ def render_label_views(occ_u8, K, c2w, hw, consts, t, empty_idx=17, stride=1, or
     V, H, W, out = _view_args('render_label_views', occ_u8, K, c2w, hw, outputs, ('depth', 'cls', 'alphainv_last', 'rgb8'), palette)
     X, Y, Z = occ_u8.shape
     ch = (ctypes.c_float * 27)(*[float(v) for v in consts])
-    _lib.call('pw_render_label_views', _chk(K, _f32, 'K'), _chk(c2w, _f32, 'c2w'), V, H, W, int(origin[0]), int(origin[1]),
-              int(stride), _chk(t, _f32, 't'), t.numel(), _ptr(occ_u8), X, Y, Z, sx, sy, sz, int(empty_idx), ch,
-              _p(out.get('depth')), _p(out.get('cls')), _p(out.get('alphainv_last')), _p(out.get('rgb8')), _p(palette),
-              0 if palette is None else palette.shape[0], _stream())
+    _lib.call('pw_render_label_views', K, c2w, V, H, W, int(origin[0]), int(origin[1]), int(stride), t, t.numel(),
+              _lib.strided(occ_u8), X, Y, Z, sx, sy, sz, int(empty_idx), ch, out.get('depth'), out.get('cls'),
+              out.get('alphainv_last'), out.get('rgb8'), palette, 0 if palette is None else palette.shape[0], _lib.STREAM)
     return out
 
 
@@ -1496,21 +1412,18 @@ def render_rays_backward(rays_o, rays_d, t, grid, consts, g_depth, g_sem, g_rgb,
         return grad_grid
     algo = algo or 'sorted'
     ch = (ctypes.c_float * 27)(*[float(v) for v in consts])
-    gw = _chk(g_weights.contiguous(), _f32, 'g_weights') if g_weights is not None else None
-    args = (_chk(rays_o.contiguous(), _f32, 'rays_o'), _chk(rays_d.contiguous(), _f32, 'rays_d'), R,
-            _chk(t, _f32, 't'), S, _chk(grid, _f32, 'grid'), X, Y, Z, GC, c_sigma, c_sem, n_sem, c_rgb, ch,
-            _chk(g_depth.contiguous(), _f32, 'g_depth'), _chk(g_sem.contiguous(), _f32, 'g_sem'),
-            _chk(g_rgb.contiguous(), _f32, 'g_rgb'), _chk(g_last.contiguous(), _f32, 'g_last'), gw)
+    gw = g_weights.contiguous() if g_weights is not None else None
+    args = (rays_o.contiguous(), rays_d.contiguous(), R, t, S, grid, X, Y, Z, GC, c_sigma, c_sem, n_sem, c_rgb, ch,
+            g_depth.contiguous(), g_sem.contiguous(), g_rgb.contiguous(), g_last.contiguous(), gw)
     if algo == 'atomics':
-        _lib.call('pw_render_rays_backward', *args, _chk(grad_grid, _f32, 'grad_grid'), _stream())
+        _lib.call('pw_render_rays_backward', *args, grad_grid, _lib.STREAM)
         return grad_grid
     g20 = torch.cat([g_sem.float(), g_rgb.float()], dim=1).contiguous()
     gmax = g20.abs().max().reshape(1).contiguous()
     nbytes = _lib.call_size('pw_render_backward_workspace_bytes', R, S, X, Y, Z, int(max_entries))
     ws = _workspace(nbytes, grid.device)
     off = (-ws.data_ptr()) % 256
-    _lib.call('pw_render_rays_backward_sorted', *args, _chk(g20, _f32, 'g_semrgb'), _chk(gmax, _f32, 'g_absmax'),
-              ctypes.c_void_p(ws.data_ptr() + off), nbytes, int(max_entries), _chk(grad_grid, _f32, 'grad_grid'), _stream())
+    _lib.call('pw_render_rays_backward_sorted', *args, g20, gmax, ws[off:], nbytes, int(max_entries), grad_grid, _lib.STREAM)
     return grad_grid
 
 
@@ -1567,7 +1480,7 @@ class _Distortion(torch.autograd.Function):
         nbytes = _lib.call_size('pw_distortion_workspace_bytes', R)
         ws = _workspace(nbytes, w.device)
         out = torch.empty(3, device=w.device, dtype=_f32)
-        _lib.call('pw_distortion_loss', _p(w), _p(s), R, S_, _p(ws), nbytes, _p(out[0:1]), _p(out[1:3]), _stream())
+        _lib.call('pw_distortion_loss', w, s, R, S_, ws, nbytes, out[0:1], out[1:3], _lib.STREAM)
         ctx.save_for_backward(w, s, out)
         return out[0]
 
@@ -1575,8 +1488,8 @@ class _Distortion(torch.autograd.Function):
     def backward(ctx, g):
         w, s, out = ctx.saved_tensors
         gw = torch.empty_like(w)
-        _lib.call('pw_distortion_loss_backward', _p(w), _p(s), w.shape[0], w.shape[1], _p(out[1:3]), _p(g.reshape(1).float().contiguous()),
-                  _p(gw), _stream())
+        _lib.call('pw_distortion_loss_backward', w, s, w.shape[0], w.shape[1], out[1:3], g.reshape(1).float().contiguous(), gw,
+                  _lib.STREAM)
         return gw, None
 
 
@@ -1603,8 +1516,7 @@ def confusion_hist(pred, gt, mask, n_cl, hist):
     m = mask.contiguous().view(-1).to(torch.uint8) if mask is not None else None
     if p.dtype != torch.uint8 or g.dtype != torch.uint8:
         raise _lib.PreworldHipError('pred/gt must be uint8')
-    _lib.call('pw_confusion_hist', _chk(p, torch.uint8, 'pred'), _chk(g, torch.uint8, 'gt'), _p(m),
-              p.numel(), int(n_cl), _chk(hist, _i64, 'hist'), _stream())
+    _lib.call('pw_confusion_hist', p, g, m, p.numel(), int(n_cl), hist, _lib.STREAM)
     return hist
 
 
@@ -1630,16 +1542,10 @@ def occ_score(preds, gts, masks, n_cl, counts):
     if tuple(counts.shape) != (H, occ_score_bins(n_cl)):
         raise _lib.PreworldHipError('occ_score: counts must be (H, n_cl*n_cl + 4) = (%d, %d), got %s'
                                     % (H, occ_score_bins(n_cl), tuple(counts.shape)))
-    keep = [_chk(p, torch.uint8, 'pred') for p in preds] + [_chk(g, torch.uint8, 'gt') for g in gts]
-    P = (ctypes.c_void_p * H)(*[p.value for p in keep[:H]])
-    G = (ctypes.c_void_p * H)(*[g.value for g in keep[H:]])
     M = None
     if masks is not None:
-        ms = [None if m is None else _chk(m.view(torch.uint8) if m.dtype == torch.bool else m, torch.uint8, 'mask') for m in masks]
-        keep += [m for m in ms if m is not None]
-        M = (ctypes.c_void_p * H)(*[None if m is None else m.value for m in ms])
-    _lib.call('pw_occ_score', P, G, M, H, n, int(n_cl), _chk(counts, _i64, 'counts'), _stream())
-    del keep
+        M = _lib.table(None if m is None else m.view(torch.uint8) if m.dtype == torch.bool else m for m in masks)
+    _lib.call('pw_occ_score', _lib.table(preds), _lib.table(gts), M, H, n, int(n_cl), counts, _lib.STREAM)
     return counts
 
 
@@ -1717,17 +1623,11 @@ def occ_fscore(preds, gts, masks, table, void=(17, 255), voxel_size=(0.4, 0.4, 0
         raise _lib.PreworldHipError('occ_fscore: table must be (H, 4) = (%d, 4), got %s' % (H, tuple(table.shape)))
     vb, ma, mc, rx, ry = _fscore_args(tuple(int(v) for v in void), tuple(float(v) for v in voxel_size), float(thr_acc),
                                       float(thr_cmpl))
-    keep = [_chk(p, torch.uint8, 'pred') for p in preds] + [_chk(g, torch.uint8, 'gt') for g in gts]
-    P = (ctypes.c_void_p * H)(*[p.value for p in keep[:H]])
-    G = (ctypes.c_void_p * H)(*[g.value for g in keep[H:]])
     M = None
     if masks is not None:
-        ms = [None if m is None else _chk(m.view(torch.uint8) if m.dtype == torch.bool else m, torch.uint8, 'mask') for m in masks]
-        keep += [m for m in ms if m is not None]
-        M = (ctypes.c_void_p * H)(*[None if m is None else m.value for m in ms])
-    _lib.call('pw_occ_fscore', P, G, M, H, shape[0], shape[1], shape[2], vb, ma, mc, rx, ry, _chk(table, _i64, 'table'),
-              _stream())
-    del keep
+        M = _lib.table(None if m is None else m.view(torch.uint8) if m.dtype == torch.bool else m for m in masks)
+    _lib.call('pw_occ_fscore', _lib.table(preds), _lib.table(gts), M, H, shape[0], shape[1], shape[2], vb, ma, mc, rx, ry, table,
+              _lib.STREAM)
     return table
 
 
@@ -1743,14 +1643,13 @@ def occ_fscore_accumulate(table, totals, empty):
     if tuple(totals.shape) != (H, 3) or tuple(empty.shape) != (H,):
         raise _lib.PreworldHipError('occ_fscore_accumulate: totals (%d, 3) float64 and empty (%d,) int64, got %s and %s'
                                     % (H, H, tuple(totals.shape), tuple(empty.shape)))
-    _lib.call('pw_occ_fscore_accumulate', _chk(t, _i64, 'table'), t.shape[0], H, _chk(totals, torch.float64, 'totals'),
-              _chk(empty, _i64, 'empty'), _stream())
+    _lib.call('pw_occ_fscore_accumulate', t, t.shape[0], H, totals, empty, _lib.STREAM)
     return totals
 
 
 # ------------------------------------------------------------------------------ camera frames to network input
-IMAGE_PREP_NPARAM = 16   # PW_IMAGE_PREP_NPARAM
-IMAGE_PREP_TILE = (32, 64)   # PW_IMAGE_PREP_TH, PW_IMAGE_PREP_TW
+IMAGE_PREP_NPARAM = _lib.PW['PW_IMAGE_PREP_NPARAM']
+IMAGE_PREP_TILE = (_lib.PW['PW_IMAGE_PREP_TH'], _lib.PW['PW_IMAGE_PREP_TW'])
 _PREC = 22
 
 
@@ -1903,9 +1802,7 @@ def prepare_images(src_u8, plan, out=None, canvas=None):
     if canvas is not None and tuple(canvas.shape) != (plan.M, fH, fW, 3):
         raise _lib.PreworldHipError('canvas must be (%d,%d,%d,3)' % (plan.M, fH, fW))
     n = ctypes.c_int(0)
-    _lib.call('pw_image_prep', _chk(src_u8, torch.uint8, 'src_u8'), plan.M, H, W, fH, fW, _chk(plan.params, _i32, 'plan.params'),
-              _chk(plan.tables, _i32, 'plan.tables'), plan.tables.numel(), plan.rows_max, int(plan.any_rot), _p(plan.ws),
-              _chk(out, _f32, 'out'), _chk(canvas, torch.uint8, 'canvas') if canvas is not None else None, ctypes.byref(n),
-              _stream())
+    _lib.call('pw_image_prep', src_u8, plan.M, H, W, fH, fW, plan.params, plan.tables, plan.tables.numel(), plan.rows_max,
+              int(plan.any_rot), plan.ws, out, canvas, ctypes.byref(n), _lib.STREAM)
     plan.launches = n.value
     return out

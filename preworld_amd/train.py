@@ -34,12 +34,6 @@ _WGRAD = 'h2'
 _DGRAD_S2 = 'h2'
 
 
-def _cl(t, name):
-    if t.dtype != _f32 or not t.is_cuda or not t.is_contiguous():
-        raise _lib.PreworldHipError('%s must be a contiguous float32 device tensor' % name)
-    return t
-
-
 # ------------------------------------------------------------------------------ raw ops
 def pack_weight(w, wino, flip_t=False):
     """ops.pack_conv_weight(w) / ops.pack_conv_weight_wino(w) -- or, with flip_t, of w.flip(2, 3, 4).transpose(0, 1) -- in one
@@ -52,8 +46,8 @@ def pack_weight(w, wino, flip_t=False):
         out = torch.empty(cin_p // 32, 64, cout_total // 16, 64, 8, device=w.device, dtype=_f32)
     else:
         out = torch.empty(cin_p // 32, k ** 3, cout_total // 32, 64, 16, device=w.device, dtype=_f32)
-    _lib.call('pw_pack_conv_weight', ops._p(_cl(w.detach().contiguous(), 'w')), Cout, Cin, k, int(bool(flip_t)), cout_total, ops._p(out),
-              int(bool(wino)), ops._stream())
+    _lib.call('pw_pack_conv_weight', w.detach().contiguous(), Cout, Cin, k, int(bool(flip_t)), cout_total, out, int(bool(wino)),
+              _lib.STREAM)
     return out
 
 
@@ -86,7 +80,7 @@ def conv3d_raw(x, w, stride=1):
     k = w.shape[2]
     if k == 2 and stride != 2:
         raise _lib.PreworldHipError('2x2x2 convs are built for stride 2 (the trajectory branch)')
-    return _conv_fwd(_cl(x, 'x'), w.detach(), stride)
+    return _conv_fwd(x, w.detach(), stride)
 
 
 def conv3d_dgrad(dy, w, x_shape, stride=1, accumulate=None):
@@ -98,7 +92,7 @@ def conv3d_dgrad(dy, w, x_shape, stride=1, accumulate=None):
     if stride == 1:
         if Cout % 32:
             raise _lib.PreworldHipError('conv3d_dgrad: Cout %% 32 == 0 expected (encoder layers)')
-        return _conv_fwd(_cl(dy, 'dy'), w, 1, flip_t=True, residual=accumulate)
+        return _conv_fwd(dy, w, 1, flip_t=True, residual=accumulate)
     if accumulate is not None:
         raise _lib.PreworldHipError('conv3d_dgrad: accumulate is built for stride 1')
     if stride != 2 or k not in (2, 3):
@@ -106,16 +100,15 @@ def conv3d_dgrad(dy, w, x_shape, stride=1, accumulate=None):
     if k == 3 and Cout % 32 == 0 and Cin % 32 == 0 and _DGRAD_S2 != 'valu':
         # the 8 parity classes of the fine grid as dense 1- to 8-tap convolutions over dY, split-fp16 operands: 27 tap products per
         # 8 fine voxels and no zero fill (round 3 inserted zeros into dY and ran the stride-1 Winograd kernel: 27 per voxel)
-        dyh = ops.f32_to_h2(_cl(dy, 'dy'))
+        dyh = ops.f32_to_h2(dy)
         nbytes = _lib.call_size('pw_conv3d_dgrad_s2_h2_workspace_bytes', Cin, Cout)
         ws = ops._workspace(nbytes, dy.device)
         dx = torch.empty(B, D, H, W, Cin, device=dy.device, dtype=_f32)
-        _lib.call('pw_conv3d_dgrad_s2_h2', ops._p(dyh.buf), ops._p(dyh.rng), ops._p(_cl(w.detach(), 'w')), ops._p(dx), ops._p(ws), nbytes,
-                  B, D, H, W, Cin, Cout, ops._stream())
+        _lib.call('pw_conv3d_dgrad_s2_h2', dyh.buf, dyh.rng, w.detach(), dx, ws, nbytes, B, D, H, W, Cin, Cout, _lib.STREAM)
         return dx
     dx = torch.empty(B, D, H, W, Cin, device=dy.device, dtype=_f32)
-    _lib.call('pw_conv3d_dgrad_s2' if k == 3 else 'pw_conv3d_dgrad_k2s2', ops._p(_cl(dy, 'dy')),
-              ops._p(_cl(w.detach().permute(2, 3, 4, 0, 1).contiguous(), 'w')), ops._p(dx), B, D, H, W, Cin, Cout, ops._stream())
+    _lib.call('pw_conv3d_dgrad_s2' if k == 3 else 'pw_conv3d_dgrad_k2s2', dy, w.detach().permute(2, 3, 4, 0, 1).contiguous(), dx, B,
+              D, H, W, Cin, Cout, _lib.STREAM)
     return dx
 
 
@@ -134,7 +127,7 @@ def _amax_of(t):
         return None
     if _AMAX_CHECK:
         fresh = torch.empty(512, device=t.device, dtype=_f32)
-        _lib.call('pw_absmax2', ops._p(_cl(t, 't')), t.numel(), ops._p(_cl(t, 't')), 0, ops._p(fresh), ops._stream())
+        _lib.call('pw_absmax2', t, t.numel(), t, 0, fresh, _lib.STREAM)
         got, want = float(rec[0].max()), float(fresh[:256].max())
         _AMAX_STATS['checked'] += 1
         assert got == want, 'recorded absmax %r does not describe the tensor (fresh pass: %r)' % (got, want)
@@ -160,20 +153,17 @@ def conv3d_wgrad(x, dy, w_shape, stride=1, x_amax=None):
         if ax is None or ay is None:
             # one pass over whichever operand did not come with its maximum recorded by the kernel that wrote it
             amax2 = torch.empty(512, device=x.device, dtype=_f32)
-            _lib.call('pw_absmax2', ops._p(_cl(x, 'x')), x.numel() if ax is None else 0, ops._p(_cl(dy, 'dy')), dy.numel() if ay is None else 0,
-                      ops._p(amax2), ops._stream())
+            _lib.call('pw_absmax2', x, x.numel() if ax is None else 0, dy, dy.numel() if ay is None else 0, amax2, _lib.STREAM)
             ax, ay = amax2[:256] if ax is None else ax, amax2[256:] if ay is None else ay
         nbytes = _lib.call_size('pw_conv3d_wgrad_h2_workspace_bytes', B, D, H, W, Cin, Cout)
         ws = ops._workspace(nbytes, x.device)
         dw = torch.empty(tuple(w_shape), device=x.device, dtype=_f32)
-        _lib.call('pw_conv3d_wgrad_h2', ops._p(_cl(x, 'x')), ops._p(_cl(dy, 'dy')), ops._p(dw), ops._p(ax), ops._p(ay), ops._p(ws), nbytes,
-                  B, D, H, W, Cin, Cout, ops._stream())
+        _lib.call('pw_conv3d_wgrad_h2', x, dy, dw, ax, ay, ws, nbytes, B, D, H, W, Cin, Cout, _lib.STREAM)
         return dw
     nbytes = _lib.call_size('pw_conv3d_wgrad_workspace_bytes', B, D, H, W, Cin, Cout, k, stride)
     ws = ops._workspace(nbytes, x.device)
     dw = torch.empty(tuple(w_shape), device=x.device, dtype=_f32)
-    _lib.call('pw_conv3d_wgrad', ops._p(_cl(x, 'x')), ops._p(_cl(dy, 'dy')), ops._p(dw), ops._p(ws), nbytes, B, D, H, W, Cin, Cout,
-              k, stride, ops._stream())
+    _lib.call('pw_conv3d_wgrad', x, dy, dw, ws, nbytes, B, D, H, W, Cin, Cout, k, stride, _lib.STREAM)
     return dw
 
 
@@ -185,18 +175,16 @@ def bn_stats(x, eps, amax=None, running=None):
     nbytes = _lib.call_size('pw_bn_workspace_bytes', C)
     ws = ops._workspace(nbytes, x.device)
     mean, var, rstd = (torch.empty(C, device=x.device, dtype=_f32) for _ in range(3))
-    _lib.call('pw_bn_stats', ops._p(_cl(x, 'x')), N, C, float(eps), ops._p(ws), nbytes, ops._p(mean), ops._p(var), ops._p(rstd),
-              ops._p(amax), ops._p(running[0]) if running else None, ops._p(running[1]) if running else None,
-              float(running[2]) if running else 0.0, ops._p(running[3]) if running and running[3] is not None else None, ops._stream())
+    _lib.call('pw_bn_stats', x, N, C, float(eps), ws, nbytes, mean, var, rstd, amax, running[0] if running else None,
+              running[1] if running else None, float(running[2]) if running else 0.0,
+              running[3] if running and running[3] is not None else None, _lib.STREAM)
     return mean, var, rstd
 
 
 def bn_apply(x, mean, rstd, gamma, beta, residual=None, relu=False, amax=None):
     C = x.shape[-1]
     y = torch.empty_like(x)
-    _lib.call('pw_bn_apply', ops._p(_cl(x, 'x')), x.numel() // C, C, ops._p(mean), ops._p(rstd), ops._p(_cl(gamma, 'gamma')),
-              ops._p(_cl(beta, 'beta')), ops._p(_cl(residual, 'residual') if residual is not None else None), int(relu), ops._p(y),
-              ops._p(amax), ops._stream())
+    _lib.call('pw_bn_apply', x, x.numel() // C, C, mean, rstd, gamma, beta, residual, int(relu), y, amax, _lib.STREAM)
     if amax is not None:
         _set_amax(y, amax)
     return y
@@ -210,13 +198,11 @@ def bn_backward(x, dy, y, mean, rstd, gamma, relu, want_dres, record_amax=False)
     nbytes = _lib.call_size('pw_bn_workspace_bytes', C)
     ws = ops._workspace(nbytes, x.device)
     s0, s1 = torch.empty(C, device=x.device, dtype=_f32), torch.empty(C, device=x.device, dtype=_f32)
-    yp = ops._p(_cl(y, 'y')) if relu else None
-    _lib.call('pw_bn_bwd_reduce', ops._p(_cl(x, 'x')), ops._p(_cl(dy, 'dy')), yp, N, C, ops._p(mean), ops._p(rstd), int(relu),
-              ops._p(ws), nbytes, ops._p(s0), ops._p(s1), ops._p(amax), ops._stream())
+    yp = y if relu else None
+    _lib.call('pw_bn_bwd_reduce', x, dy, yp, N, C, mean, rstd, int(relu), ws, nbytes, s0, s1, amax, _lib.STREAM)
     dx = torch.empty_like(x)
     dres = torch.empty_like(x) if want_dres else None
-    _lib.call('pw_bn_bwd_apply', ops._p(x), ops._p(dy), yp, N, C, ops._p(mean), ops._p(rstd), ops._p(_cl(gamma, 'gamma')),
-              ops._p(s0), ops._p(s1), int(relu), ops._p(dx), ops._p(dres), ops._p(amax), ops._stream())
+    _lib.call('pw_bn_bwd_apply', x, dy, yp, N, C, mean, rstd, gamma, s0, s1, int(relu), dx, dres, amax, _lib.STREAM)
     if amax is not None:
         _set_amax(dx, amax)
     return dx, s1, s0, dres
@@ -320,16 +306,14 @@ class BatchNormCL(torch.autograd.Function):
         nbytes = _lib.call_size('pw_bn_workspace_bytes', C)
         ws = ops._workspace(nbytes, x.device)
         s0, s1 = torch.empty(C, device=x.device, dtype=_f32), torch.empty(C, device=x.device, dtype=_f32)
-        yp = ops._p(_cl(y, 'y')) if ctx.relu else None
-        _lib.call('pw_bn_bwd_reduce', ops._p(_cl(x, 'x')), ops._p(_cl(dy, 'dy')), yp, N, C, ops._p(mean), ops._p(rstd), int(ctx.relu),
-                  ops._p(ws), nbytes, ops._p(s0), ops._p(s1), None, ops._stream())
+        yp = y if ctx.relu else None
+        _lib.call('pw_bn_bwd_reduce', x, dy, yp, N, C, mean, rstd, int(ctx.relu), ws, nbytes, s0, s1, None, _lib.STREAM)
         tot = _all_reduce_sum(torch.cat([s0, s1]).double()) * ctx.n_ratio
         g0, g1 = tot[:C].float().contiguous(), tot[C:].float().contiguous()
         dx = torch.empty_like(x)
         want_dres = ctx.has_res and ctx.needs_input_grad[3]
         dres = torch.empty_like(x) if want_dres else None
-        _lib.call('pw_bn_bwd_apply', ops._p(x), ops._p(dy), yp, N, C, ops._p(mean), ops._p(rstd), ops._p(_cl(g, 'gamma')),
-                  ops._p(g0), ops._p(g1), int(ctx.relu), ops._p(dx), ops._p(dres), None, ops._stream())
+        _lib.call('pw_bn_bwd_apply', x, dy, yp, N, C, mean, rstd, g, g0, g1, int(ctx.relu), dx, dres, None, _lib.STREAM)
         return dx, s1, s0, dres, None, None, None, None
 
 
@@ -340,9 +324,9 @@ def _update_running(bn, mean, var, n):
         return
     if bn.momentum is not None and bn.running_mean.is_cuda and bn.running_mean.dtype == _f32 and bn.running_var.dtype == _f32:
         on_dev = torch.is_tensor(n)
-        _lib.call('pw_bn_update_running', ops._p(mean), ops._p(var), mean.numel(), 0.0 if on_dev else float(n),
-                  ops._p(n.float().contiguous()) if on_dev else None, float(bn.momentum), ops._p(bn.running_mean), ops._p(bn.running_var),
-                  ops._p(bn.num_batches_tracked) if bn.num_batches_tracked is not None else None, ops._stream())
+        _lib.call('pw_bn_update_running', mean, var, mean.numel(), 0.0 if on_dev else float(n),
+                  n.float().contiguous() if on_dev else None, float(bn.momentum), bn.running_mean, bn.running_var,
+                  bn.num_batches_tracked, _lib.STREAM)
         return
     with torch.no_grad():
         bn.num_batches_tracked += 1
@@ -363,7 +347,7 @@ class ConvPairCL(torch.autograd.Function):
     def forward(ctx, x, w1, w2, stride):
         ctx.save_for_backward(x, w1, w2)
         ctx.stride, ctx.x_amax = stride, _amax_of(x)
-        return _conv_fwd_pair(_cl(x, 'x'), w1.detach(), w2.detach(), stride)
+        return _conv_fwd_pair(x, w1.detach(), w2.detach(), stride)
 
     @staticmethod
     def backward(ctx, dy1, dy2):
@@ -378,7 +362,7 @@ class ConvPairCL(torch.autograd.Function):
         xa = ctx.x_amax
         if xa is None and ctx.stride == 1 and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]:
             xa = torch.empty(512, device=x.device, dtype=_f32)           # one pass over x serves both weight gradients
-            _lib.call('pw_absmax2', ops._p(x), x.numel(), ops._p(x), 0, ops._p(xa), ops._stream())
+            _lib.call('pw_absmax2', x, x.numel(), x, 0, xa, _lib.STREAM)
             xa = xa[:256]
         dw1 = conv3d_wgrad(x, dy1, w1.shape, ctx.stride, xa) if ctx.needs_input_grad[1] else None
         dw2 = conv3d_wgrad(x, dy2, w2.shape, ctx.stride, xa) if ctx.needs_input_grad[2] else None
@@ -436,8 +420,8 @@ def basic_block_forward(blk, x):
 def upsample_add(lo, hi, accumulate):
     """hi (B,Dh,Hh,Wh,C) (+)= trilinear(lo (B,Dl,Hl,Wl,C)), align_corners=True (torch's index rule)"""
     B, Dl, Hl, Wl, C = lo.shape
-    _lib.call('pw_upsample_trilinear_add', ops._p(_cl(lo, 'lo')), ops._p(_cl(hi, 'hi')), B, Dl, Hl, Wl, hi.shape[1], hi.shape[2],
-              hi.shape[3], C, int(accumulate), ops._stream())
+    _lib.call('pw_upsample_trilinear_add', lo, hi, B, Dl, Hl, Wl, hi.shape[1], hi.shape[2], hi.shape[3], C, int(accumulate),
+              _lib.STREAM)
     return hi
 
 
@@ -447,7 +431,7 @@ def upsample_adjoint(dhi, lo_shape):
     dims = (B, Dl, Hl, Wl, dhi.shape[1], dhi.shape[2], dhi.shape[3], C)
     nbytes = _lib.call_size('pw_upsample_trilinear_adjoint_workspace_bytes', *dims)
     ws = ops._workspace(nbytes, dhi.device)
-    _lib.call('pw_upsample_trilinear_adjoint', ops._p(_cl(dhi, 'dhi')), ops._p(dlo), ops._p(ws), nbytes, *dims, ops._stream())
+    _lib.call('pw_upsample_trilinear_adjoint', dhi, dlo, ws, nbytes, *dims, _lib.STREAM)
     return dlo
 
 
@@ -485,7 +469,7 @@ class BiasActCL(torch.autograd.Function):
         C = x.shape[-1]
         b = bias.detach().float().contiguous() if bias is not None else None
         y = torch.empty_like(x)
-        _lib.call('pw_bias_act', ops._p(_cl(x, 'x')), ops._p(b), x.numel() // C, C, _ACT[act], ops._p(y), ops._stream())
+        _lib.call('pw_bias_act', x, b, x.numel() // C, C, _ACT[act], y, _lib.STREAM)
         ctx.save_for_backward(x, b if b is not None else torch.empty(0))
         ctx.act, ctx.has_bias = _ACT[act], b is not None
         return y
@@ -499,8 +483,8 @@ class BiasActCL(torch.autograd.Function):
         db = torch.empty(C, device=x.device, dtype=_f32) if want_db else None
         nbytes = _lib.call_size('pw_bias_act_workspace_bytes', C)
         ws = ops._workspace(nbytes, x.device)
-        _lib.call('pw_bias_act_backward', ops._p(x), ops._p(b) if ctx.has_bias else None, ops._p(_cl(dy.contiguous(), 'dy')), x.numel() // C, C,
-                  ctx.act, ops._p(dx), ops._p(db), ops._p(ws), nbytes, ops._stream())
+        _lib.call('pw_bias_act_backward', x, b if ctx.has_bias else None, dy.contiguous(), x.numel() // C, C, ctx.act, dx, db, ws,
+                  nbytes, _lib.STREAM)
         return dx, db, None
 
 
@@ -538,7 +522,7 @@ def _linear_rows(x, w):
     """x (..., K) channels-last, w (N, K) -> (..., N) on pw_linear_rows"""
     K, N = w.shape[1], w.shape[0]
     y = torch.empty(tuple(x.shape[:-1]) + (N,), device=x.device, dtype=_f32)
-    _lib.call('pw_linear_rows', ops._p(_cl(x, 'x')), ops._p(w.contiguous()), ops._p(y), x.numel() // K, K, N, ops._stream())
+    _lib.call('pw_linear_rows', x, w.contiguous(), y, x.numel() // K, K, N, _lib.STREAM)
     return y
 
 

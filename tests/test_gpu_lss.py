@@ -475,7 +475,7 @@ def test_lift_pool_with_non_contiguous_camera_tensors():
     """Round 6 regression (found by the reference-class B = 2 training fixtures): prepare_inputs hands the view transformer per-frame
     SLICES of the (B, T, N, ...) pose tensors -- non-contiguous as soon as B > 1 -- and ops.lss_lift_pool made contiguous temporaries
     whose addresses outlived them: the four camera tensors of a call aliased one allocator block.  The pointer arguments now keep
-    their tensors alive (ops._Ptr); strided inputs must give the bits of contiguous ones."""
+    their tensors alive (the tensors are the arguments of _lib.call); strided inputs must give the bits of contiguous ones."""
     gc, N, B, rig = _rig_cfg('full_adj_b2')
     fr, lower, interval, size, vox, coor = _prepare(gc, S.INPUT_SIZE, S.DOWNSAMPLE, rig, B, N)
     depth, feat = S.lift_inputs(7, B=B, N=N)

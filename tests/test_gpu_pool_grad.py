@@ -386,10 +386,10 @@ def test_argument_errors_launch_nothing():
     ops.bev_pool_v2_backward(g, dg, fg, d, f, rd, rf, rb, empty, empty)
     ops.bev_pool_v2_forward(d, f, out, T(ranks.ranks_depth), T(ranks.ranks_feat), T(ranks.ranks_bev), empty, empty)
     assert untouched()
-    p, st_ = ops._p, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st_ = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     n_int = int(ln.numel())
-    bwd = [p(g), p(dg), p(fg), p(d), p(f), p(rd), p(rf), p(rb), p(ln), p(st)]
-    fwd = [p(d), p(f), p(out), p(rd), p(rf), p(rb), p(ln), p(st)]
+    bwd = [g, dg, fg, d, f, rd, rf, rb, ln, st]
+    fwd = [d, f, out, rd, rf, rb, ln, st]
     for i in range(len(bwd)):                                            # a null pointer in any position
         args = list(bwd)
         args[i] = None
