@@ -344,6 +344,7 @@ k_forecast_h2(const float* __restrict__ v0, long long n_vox_per_sample, int n_sa
 #pragma unroll
   for (int s = 0; s < 16; ++s) b2r[s] = fb2[row_of(s, h)] * rng_pow2(-eu);
   float amax = 0.f;
+  unsigned lastbits = 0u;                    // |bits| of every voxel's last state: the non-finite ones `amax` cannot carry
   // A fragment (t, k-block, plane) of this lane: 16 bytes at ((t*2 + kb)*2 + p)*1024 + lane*16
   const char* a1 = reinterpret_cast<const char*>(l_w1) + lane * 16;
   const char* a2 = reinterpret_cast<const char*>(l_w2) + lane * 16;
@@ -491,8 +492,16 @@ k_forecast_h2(const float* __restrict__ v0, long long n_vox_per_sample, int n_sa
         }
       }
     }
+    // v_max_f32 drops a NaN, so `amax` alone would leave a slot that looks healthy over states full of NaN (pw_h2.h: a NaN is recorded
+    // as such).  NaN and Inf are sticky through the residual recursion: the LAST state of a voxel tells, once per trip instead of per step.
+#pragma unroll
+    for (int u = 0; u < NU; ++u)
+      if (valid[u]) {
+#pragma unroll
+        for (int s = 0; s < 16; ++s) lastbits = max(lastbits, rng_absbits(v[u][s]));
+      }
   }
-  rng_note(st_rng, __float_as_uint(amax), eu);
+  rng_note(st_rng, max(__float_as_uint(amax), lastbits), eu);
 }
 
 PW_API int pw_forecast_steps_h2(const float* v0, int64_t n_vox_per_sample, int n_samples, const float* w1p,

@@ -428,6 +428,7 @@ class RangeCtx:
         self.sticky = torch.zeros(4, dtype=_i32, device=device)                 # audit(): [bad slots, bad passes, passes audited, -]
         self.n = 0
         self.device = torch.device(device)
+        self._jumped = set()             # slots whose last settle() step was the + 12 of a non-finite maximum
 
     def begin(self):
         """start of a pass: slots are handed out from 0 again, recorded maxima are cleared (a kernel, capturable)"""
@@ -486,11 +487,17 @@ class RangeCtx:
         for i in range(len(e)):
             a = float(amax[i])
             if a == 0.0:
+                self._jumped.discard(i)               # not written in this pass: a later user of the index starts afresh
                 continue
             if not np.isfinite(a):                    # overflowed under this exponent (or fed by a tensor that did)
                 new[i] = min(int(e[i]) + 12, 100)
+                self._jumped.add(i)
                 continue
             ideal = self.ideal_exp(a)
+            if i in self._jumped:                     # the blind + 12 only brought the tensor back into sight: with a finite maximum known,
+                self._jumped.discard(i)               # take ITS ideal exponent instead of whatever the jump landed on inside the window
+                new[i] = ideal
+                continue
             if not (ideal + self.TARGET - self.SETTLE_HI < e[i] <= ideal + self.TARGET - self.SETTLE_LO):
                 new[i] = ideal
         if (new == e).all():
