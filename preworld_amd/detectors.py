@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import builder, ops
-from .modules import (ConvModule3d, DownScaleModule3DCustom, _PackedCache, as_f32, precision, to_channels_last_3d)
+from .modules import (ConvModule3d, Derived, DownScaleModule3DCustom, as_f32, precision, to_channels_last_3d)
 
 
 # occ3d-nuScenes voxel counts per class (mmdet3d/models/detectors/preworld.py:19-21): class weights 1 / log(freq)
@@ -61,7 +61,7 @@ class BEVStereo4DOCC(nn.Module):
             self.predicter = nn.Sequential(nn.Linear(out_dim, out_dim * 2), nn.Softplus(),
                                            nn.Linear(out_dim * 2, num_classes))
         self.loss_occ_cfg = loss_occ
-        self._pred_cache = _PackedCache()
+        self._derived = Derived()
 
     # ---- bevdet_occ.py:88-139 (BEVStereo4DOCC.prepare_inputs): split the stacked inputs into
     # frames and express every sweep's sensor pose in the KEY frame's ego system (fp64 algebra)
@@ -398,13 +398,14 @@ class BEVStereo4DOCC(nn.Module):
     def simple_test_from_lift(self, frames, **kwargs):
         return self._ranged(lambda: self._simple_test_from_lift(frames, **kwargs))
 
+    def _predicter_packed(self):
+        p = self.predicter
+        return self._derived.get('pred', (p[0], p[2]), lambda: ops.pack_mlp_blocks([p]))
+
     def _simple_test_from_lift(self, frames, **kwargs):
         v = self.extract_voxel_feat_cl(frames)
         if self.use_predicter:
-            p = self.predicter
-            packed = self._pred_cache.get([p[0].weight, p[0].bias, p[2].weight, p[2].bias],
-                                          lambda: ops.pack_mlp_blocks([p]))
-            v = ops.attr_mlp(v, packed, final_softplus=False)[..., :self.num_classes]
+            v = ops.attr_mlp(v, self._predicter_packed(), final_softplus=False)[..., :self.num_classes]
         occ = v.argmax(-1).to(torch.uint8).permute(0, 3, 2, 1)         # (B,X,Y,Z)
         return [occ.squeeze(0)]
 
@@ -483,16 +484,15 @@ class _PreWorldCommon(BEVStereo4DOCC):
         if use_focal_loss:
             self.focal_loss = builder.build(dict(type='CustomFocalLoss'))
 
+    def _attr_packed(self):
+        mods = (self.density_mlp, self.semantic_mlp, self.color_mlp)
+        return self._derived.get('attr', [m[i] for m in mods for i in (0, 2)], lambda: ops.pack_attr_mlp(*mods))
+
     # ---- preworld_temporal_traj.py:231-236: density / semantic / color MLPs, fused
     def attributes_cl(self, v_cl):
         """v_cl (B,Z,Y,X,C) -> packed grid (B,Z,Y,X,24): [0:2] density_prob, [2:19] semantic,
         [19:22] color.  `grid[..., 0]` is the reference's `density`."""
-        mods = (self.density_mlp, self.semantic_mlp, self.color_mlp)
-        params = [m[i].weight for m in mods for i in (0, 2)] + [m[i].bias for m in mods for i in (0, 2)]
-        if not hasattr(self, '_attr_cache'):
-            self._attr_cache = _PackedCache()
-        packed = self._attr_cache.get(params, lambda: ops.pack_attr_mlp(*mods))
-        return ops.attr_mlp(v_cl, packed, final_softplus=len(self.density_mlp) == 4)
+        return ops.attr_mlp(v_cl, self._attr_packed(), final_softplus=len(self.density_mlp) == 4)
 
     # ---- preworld_temporal_traj.py:237-250: occupancy from density threshold + semantic argmax
     def attribute_decode(self, grid):
@@ -709,7 +709,6 @@ class PreWorld4DTraj(_PreWorldCommon):
                                              nn.Linear(out_dim * 2, out_dim))
         self.traj_head = nn.Sequential(nn.Linear(out_dim, out_dim * 2), nn.Softplus(),
                                        nn.Linear(out_dim * 2, 2))
-        self._fc_cache = _PackedCache()
 
     def set_epoch(self, epoch):
         self.curr_epoch = epoch
@@ -728,11 +727,13 @@ class PreWorld4DTraj(_PreWorldCommon):
         t = ops.linear_act(fused_ego.contiguous(), th[0].weight.contiguous(), th[0].bias, 'softplus')
         return ops.linear_act(t, th[2].weight.contiguous(), th[2].bias), fused_ego
 
-    def _forecast_weights(self):
-        fh = self.fusion_head
-        return self._fc_cache.get([fh[0].weight, fh[2].weight],
-                                  lambda: ops.forecast_pack(fh[0].weight.float().contiguous(),
-                                                            fh[2].weight.float().contiguous()))
+    def _forecast_weights(self, kind):
+        """the fusion head's two weight matrices packed for ops.forecast_steps ('fc') / ops.forecast_steps_h2 ('fc_h2'); its biases go
+        to the kernels live"""
+        w1, w2 = self.fusion_head[0].weight, self.fusion_head[2].weight
+        if kind == 'fc_h2':
+            return self._derived.get(kind, (w1, w2), lambda: ops.forecast_pack_h2(w1.float(), w2.float()))
+        return self._derived.get(kind, (w1, w2), lambda: ops.forecast_pack(w1.float().contiguous(), w2.float().contiguous()))
 
     # ---- preworld_temporal_traj.py:329-368: all recursion steps in one kernel
     def forecast_cl(self, v_cl, ego_states, n_steps=6, out_h2=False, prologue=None):
@@ -753,14 +754,10 @@ class PreWorld4DTraj(_PreWorldCommon):
         else:
             ef, _, c1p = ops.forecast_prologue(ego, plan, fh[0].weight.contiguous(), fh[0].bias)
         if precision() == 'h2':
-            if not hasattr(self, '_fc_h2cache'):
-                self._fc_h2cache = _PackedCache()
-            packed = self._fc_h2cache.get([fh[0].weight, fh[2].weight],
-                                          lambda: ops.forecast_pack_h2(fh[0].weight.float(), fh[2].weight.float()))
-            return ops.forecast_steps_h2(v_cl, B, packed, c1p, fh[2].bias, n_steps, out_h2=out_h2), ef
+            return ops.forecast_steps_h2(v_cl, B, self._forecast_weights('fc_h2'), c1p, fh[2].bias, n_steps, out_h2=out_h2), ef
         if isinstance(v_cl, ops.H2):
             v_cl = ops.h2_to_f32(v_cl)
-        w1p, w2p = self._forecast_weights()
+        w1p, w2p = self._forecast_weights('fc')
         states = ops.forecast_steps(v_cl, B, w1p, w2p, c1p, fh[2].bias, n_steps)
         return states, ef
 

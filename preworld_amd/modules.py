@@ -57,7 +57,7 @@ class LSSViewTransformer(nn.Module):
         self.accelerate = accelerate
         self.initial_flag = True
         self.collapse_z = collapse_z
-        self._cache = None
+        self._derived = Derived()
 
     # ---- view_transformer.py:66-82
     def create_grid_infos(self, x, y, z, **kwargs):
@@ -72,11 +72,9 @@ class LSSViewTransformer(nn.Module):
         return fr
 
     def _grid(self):
-        key = tuple((id(t), t._version, t.data_ptr()) for t in (self.grid_lower_bound, self.grid_interval, self.grid_size))
-        if getattr(self, '_grid_host', (None,))[0] != key:                 # host copies of the three 3-vectors, made once
-            self._grid_host = (key, ([float(v) for v in self.grid_lower_bound], [float(v) for v in self.grid_interval],
-                                     [int(v) for v in self.grid_size]))
-        return self._grid_host[1]
+        lower, interval, size = self.grid_lower_bound, self.grid_interval, self.grid_size
+        return self._derived.get('grid', (lower, interval, size),          # host copies of the three 3-vectors, made once
+                                 lambda: ([float(v) for v in lower], [float(v) for v in interval], [int(v) for v in size]))
 
     def _frustum_on(self, ref):
         if self.frustum.device != ref.device:
@@ -96,21 +94,12 @@ class LSSViewTransformer(nn.Module):
 
     def _sort(self, sensor2ego, cam2imgs, post_rots, post_trans, bda):
         """geometry -> voxel ids -> device counting sort.  With accelerate=True the result is kept and reused for as
-        long as the camera tensors are the SAME tensors with unchanged contents (identity + torch version counters;
+        long as the camera tensors are the SAME tensors with unchanged contents (tensor_key;
         the reference's accelerate flag, view_transformer.py:155-174,263-267, assumes a fixed rig and never checks)."""
-        key = None
+        cams = (sensor2ego, cam2imgs, post_rots, post_trans, bda)
         if self.accelerate:
-            tensors = (sensor2ego, cam2imgs, post_rots, post_trans, bda)
-            # identity + version counter of the tensor OBJECTS, which the cache entry keeps alive: a freed tensor's address can be
-            # handed to a new one by the caching allocator (with _version 0 again), so addresses alone would alias (ADVICE r02)
-            # (+ the data pointer: `t.data = other` swaps the storage without touching id or _version, ADVICE r03)
-            key = tuple((id(t), t._version, t.data_ptr()) for t in tensors)
-            if self._cache is not None and self._cache[0] == key:
-                return self._cache[2]
-        vs = self._sort_now(sensor2ego, cam2imgs, post_rots, post_trans, bda)
-        if key is not None:
-            self._cache = (key, tensors, vs)
-        return vs
+            return self._derived.get('sort', cams, lambda: self._sort_now(*cams))
+        return self._sort_now(*cams)
 
     def _sort_now(self, sensor2ego, cam2imgs, post_rots, post_trans, bda):
         B, N = sensor2ego.shape[:2]
@@ -339,23 +328,50 @@ def _use_wino(x_cl, cout_total, ksize, stride):
     return B * ((D + 3) // 4) * ((H + 7) // 8) * ((W + 7) // 8) * (cout_total // 32) >= 128
 
 
-class _PackedCache:
-    """Packed/folded weights are derived data: rebuilt lazily when parameters change."""
+def tensor_key(tensors):
+    """what "these are still the tensors I derived from" means: identity + version counter of the tensor OBJECTS, which the holder of
+    the key keeps alive -- a freed tensor's address can be handed to a new one by the caching allocator (with _version 0 again), so
+    addresses alone would alias; + the data pointer: `t.data = other` swaps the storage without touching id or _version
+    (ADVICE r03); + the device: an empty tensor's data pointer is 0 wherever it lives."""
+    return tuple((id(t), t._version, t.data_ptr(), t.device) for t in tensors)
+
+
+def tensors_of(*sources):
+    """flat list of the tensors that `sources` stand for: a tensor is itself, None is nothing, an nn.Module is its floating-point
+    parameters and buffers in registration order, its own before its children's (num_batches_tracked and other integer buffers
+    are no operand of any kernel).  Reads the modules' dicts directly: this runs at every lookup of the eager path."""
+    out = []
+    for s in sources:
+        if s is None:
+            continue
+        if isinstance(s, torch.Tensor):
+            out.append(s)
+            continue
+        for d in (s._parameters, s._buffers):
+            for t in d.values():
+                if t is not None and t.is_floating_point():
+                    out.append(t)
+        if s._modules:
+            out += tensors_of(*s._modules.values())
+    return out
+
+
+class Derived:
+    """A module's derived operands (packed / folded weights, host copies of small buffers), one entry per name: built on first use,
+    rebuilt when tensor_key of the entry's sources changes.  The entry holds the source tensors themselves, so neither their ids
+    nor their addresses can be recycled under it."""
 
     def __init__(self):
-        self._key = None
-        self._val = None
-        self._live = None
+        self._entries = {}
 
-    def get(self, tensors, build):
-        # identity + version of the parameter OBJECTS (kept alive by the entry; see LSSViewTransformer._sort for why not addresses)
-        live = [t for t in tensors if t is not None]
-        key = tuple((id(t), t._version, t.data_ptr(), t.device) for t in live)
-        if key != self._key:
+    def get(self, name, sources, build):
+        live = tensors_of(*sources)
+        key = tensor_key(live)
+        entry = self._entries.get(name)
+        if entry is None or entry[0] != key:
             with torch.no_grad():
-                self._val = build()
-            self._key, self._live = key, live
-        return self._val
+                entry = self._entries[name] = (key, live, build())
+        return entry[2]
 
 
 class ConvModule3d(nn.Module):
@@ -382,39 +398,33 @@ class ConvModule3d(nn.Module):
         self.in_channels, self.out_channels = in_channels, out_channels
         self.kernel_size, self.stride, self.padding = kernel_size, stride, padding
         assert padding == kernel_size // 2
-        self._cache = _PackedCache()
-        self._wcache = _PackedCache()
+        self._derived = Derived()
+
+    def operands(self, kind):
+        """the conv's device operands: 'f32' (packed weight, scale[cout32], bias[cout32]) for the direct HIP conv, 'wino' the same with
+        the Winograd-domain weight, 'h2' (split-fp16 packed weight, scale * weight pre-scale, bias) for ops.conv3d_h2."""
+        conv, bn = self.conv, self.bn if self.with_norm else None
+
+        def build():
+            if kind == 'f32':
+                if bn is not None:
+                    sc, bi = ops.fold_bn(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, conv.bias)
+                else:
+                    sc = torch.ones_like(conv.weight[:, 0, 0, 0, 0])
+                    bi = conv.bias.float() if conv.bias is not None else torch.zeros_like(sc)
+                return ops.pack_conv_weight(conv.weight), ops._pad32(sc, 1.0), ops._pad32(bi, 0.0)
+            _, sc, bi = self.operands('f32')
+            if kind == 'wino':
+                return ops.pack_conv_weight_wino(conv.weight), sc, bi
+            wpk, inv = ops.pack_conv_weight_h2(conv.weight)
+            return wpk, (sc * inv).contiguous(), bi
+        return self._derived.get(kind, (conv, bn), build)
 
     def folded(self):
-        """(packed weight, scale[cout32], bias[cout32]) for the HIP conv."""
-        params = [self.conv.weight, self.conv.bias]
-        if self.with_norm:
-            params += [self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var]
-
-        def build():
-            wpk = ops.pack_conv_weight(self.conv.weight)
-            if self.with_norm:
-                sc, bi = ops.fold_bn(self.bn.weight, self.bn.bias, self.bn.running_mean,
-                                     self.bn.running_var, self.bn.eps, self.conv.bias)
-            else:
-                sc = torch.ones_like(self.conv.weight[:, 0, 0, 0, 0])
-                bi = self.conv.bias.float() if self.conv.bias is not None else torch.zeros_like(sc)
-            return wpk, ops._pad32(sc, 1.0), ops._pad32(bi, 0.0)
-        return self._cache.get(params, build)
+        return self.operands('f32')
 
     def folded_h2(self):
-        """(split-fp16 packed weight, scale * weight pre-scale, bias) for ops.conv3d_h2."""
-        params = [self.conv.weight, self.conv.bias]
-        if self.with_norm:
-            params += [self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var]
-        if not hasattr(self, '_h2cache'):
-            self._h2cache = _PackedCache()
-
-        def build():
-            _, sc, bi = self.folded()
-            wpk, inv = ops.pack_conv_weight_h2(self.conv.weight)
-            return wpk, (sc * inv).contiguous(), bi
-        return self._h2cache.get(params, build)
+        return self.operands('h2')
 
     def _check_eval(self):
         if self.training and self.with_norm:
@@ -443,7 +453,7 @@ class ConvModule3d(nn.Module):
     def _forward_cl_f32(self, x_cl, residual=None, algo=0):
         wpk, sc, bi = self.folded()
         if algo == 0 and _use_wino(x_cl, sc.numel(), self.kernel_size, self.stride):
-            uw = self._wcache.get([self.conv.weight], lambda: ops.pack_conv_weight_wino(self.conv.weight))
+            uw, sc, bi = self.operands('wino')
             return ops.conv3d_wino(x_cl, uw, sc, bi, residual=residual, cout0=self.out_channels,
                                    relu0=self.with_activation)
         return ops.conv3d_ndhwc(x_cl, wpk, sc, bi, residual=residual, cout0=self.out_channels,
@@ -467,7 +477,17 @@ class BasicBlock3D(nn.Module):
                                   conv_cfg=dict(type='Conv3d'), norm_cfg=dict(type='BN3d'),
                                   act_cfg=None)
         self.downsample = downsample
-        self._cache = _PackedCache()
+        self._derived = Derived()
+
+    def pair_operands(self, kind):
+        """conv1 + downsample side by side (they read the same input: ONE conv with 2 x Cout columns): the two convs' own
+        operands of `kind` ('f32', 'wino', 'h2'), concatenated along the packed output columns."""
+        c1, ds = self.conv1, self.downsample
+
+        def build():
+            (w1, s1, b1), (wd, sd, bd) = c1.operands(kind), ds.operands(kind)
+            return (torch.cat([w1, wd], dim=2).contiguous(), torch.cat([s1, sd]).contiguous(), torch.cat([b1, bd]).contiguous())
+        return self._derived.get(kind, (c1, ds), build)
 
     def forward_cl(self, x, out=None, out_h2=False):
         """x: fp32 channels-last tensor or ops.H2.  out: optional destination (a channel slice of a wider channels-last
@@ -497,17 +517,7 @@ class BasicBlock3D(nn.Module):
         c1._check_eval()
         x = as_h2(x)
         if ds is not None:
-            params = [c1.conv.weight, c1.bn.weight, c1.bn.bias, c1.bn.running_mean, c1.bn.running_var,
-                      ds.conv.weight, ds.bn.weight, ds.bn.bias, ds.bn.running_mean, ds.bn.running_var]
-            if not hasattr(self, '_h2cache'):
-                self._h2cache = _PackedCache()
-
-            def build():
-                w1, s1, b1 = c1.folded_h2()
-                wd, sd, bd = ds.folded_h2()
-                return (torch.cat([w1, wd], dim=2).contiguous(), torch.cat([s1, sd]).contiguous(),
-                        torch.cat([b1, bd]).contiguous())
-            wpk, sc, bi = self._h2cache.get(params, build)
+            wpk, sc, bi = self.pair_operands('h2')
             y, identity = ops.conv3d_h2(x, wpk, sc, bi, cout0=c1.out_channels, cout1=ds.out_channels, relu0=True, relu1=False,
                                         out1=out, ksize=3, stride=c1.stride, out_h2=(True, out_h2))
         else:
@@ -529,20 +539,9 @@ class BasicBlock3D(nn.Module):
         c1, c2, ds = self.conv1, self.conv2, self.downsample
         c1._check_eval()
         if ds is not None:
-            params = [c1.conv.weight, c1.bn.weight, c1.bn.bias, c1.bn.running_mean, c1.bn.running_var,
-                      ds.conv.weight, ds.bn.weight, ds.bn.bias, ds.bn.running_mean, ds.bn.running_var]
-
-            def build():
-                w1, s1, b1 = c1.folded()
-                wd, sd, bd = ds.folded()
-                return (torch.cat([w1, wd], dim=2).contiguous(), torch.cat([s1, sd]).contiguous(),
-                        torch.cat([b1, bd]).contiguous())
-            wpk, sc, bi = self._cache.get(params, build)
+            wpk, sc, bi = self.pair_operands('f32')
             if _use_wino(x, sc.numel(), 3, c1.stride):
-                if not hasattr(self, '_wcache'):
-                    self._wcache = _PackedCache()
-                uw = self._wcache.get([c1.conv.weight, ds.conv.weight],
-                                      lambda: ops.pack_conv_weights_wino_concat([c1.conv.weight, ds.conv.weight]))
+                uw, sc, bi = self.pair_operands('wino')
                 y, identity = ops.conv3d_wino(x, uw, sc, bi, cout0=c1.out_channels, cout1=ds.out_channels,
                                               relu0=True, relu1=False, out1=out)
             else:
@@ -557,7 +556,7 @@ class BasicBlock3D(nn.Module):
             out.copy_(identity)
             identity = out
         if _use_wino(y, s2.numel(), 3, 1):
-            uw2 = c2._wcache.get([c2.conv.weight], lambda: ops.pack_conv_weight_wino(c2.conv.weight))
+            uw2, s2, b2 = c2.operands('wino')
             return ops.conv3d_wino(y, uw2, s2, b2, residual=identity, cout0=c2.out_channels, relu0=True, out0=out)
         return ops.conv3d_ndhwc(y, w2, s2, b2, residual=identity, cout0=c2.out_channels, ksize=3,
                                 stride=1, relu0=True, out0=out)
@@ -625,7 +624,24 @@ class LSSFPN3D(nn.Module):
                                  conv_cfg=dict(type='Conv3d'), norm_cfg=dict(type='BN3d'),
                                  act_cfg=dict(type='ReLU', inplace=True))
         self.with_cp = with_cp
-        self._cache = _PackedCache()
+        self._derived = Derived()
+
+    def operands(self, kind, c8, c16):
+        """the 1x1x1 conv split by input level (channels [0, c8), [c8, c8 + c16) and the rest), packed per level, + the folded BN:
+        'f32' (w8, w16, w32, scale, bias); 'h2' (w8, w16, w32, r16, r32, scale8, bias) -- the three partial sums share ONE BN scale:
+        y16 / y32 are scaled by r16 = inv16 / inv8 and r32 = inv32 / inv8 so that the fused kernel can apply scale8 = scale * inv8
+        to the sum (all factors are powers of two: exact)."""
+        cm = self.conv
+
+        def build():
+            w, bn = cm.conv.weight, cm.bn
+            sc, bi = ops.fold_bn(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
+            ws = [w[:, :c8].contiguous(), w[:, c8:c8 + c16].contiguous(), w[:, c8 + c16:].contiguous()]
+            if kind == 'f32':
+                return tuple(ops.pack_conv_weight(wl) for wl in ws) + (sc, bi)
+            (w8, i8), (w16, i16), (w32, i32) = [ops.pack_conv_weight_h2(wl) for wl in ws]
+            return w8, w16, w32, (i16 / i8).contiguous(), (i32 / i8).contiguous(), (sc * i8).contiguous(), bi
+        return self._derived.get((kind, c8, c16), (cm,), build)
 
     def forward_cl(self, feats, out_h2=False):
         """feats: fp32 channels-last tensors or ops.H2 -> fp32 tensor (or ops.H2 with out_h2)"""
@@ -634,35 +650,14 @@ class LSSFPN3D(nn.Module):
             return train.fpn_forward(self, [as_f32(f) for f in feats])
         x8, x16, x32 = feats
         c8, c16, c32 = x8.shape[-1], x16.shape[-1], x32.shape[-1]
-        cm = self.conv
-        cm._check_eval()
-        params = [cm.conv.weight, cm.bn.weight, cm.bn.bias, cm.bn.running_mean, cm.bn.running_var]
-        w = cm.conv.weight
-        assert w.shape[1] == c8 + c16 + c32
+        self.conv._check_eval()
+        assert self.conv.conv.weight.shape[1] == c8 + c16 + c32
         if precision() == 'h2':
-            if not hasattr(self, '_h2cache'):
-                self._h2cache = _PackedCache()
-
-            def build_h2():
-                sc, bi = ops.fold_bn(cm.bn.weight, cm.bn.bias, cm.bn.running_mean, cm.bn.running_var, cm.bn.eps)
-                w8, i8 = ops.pack_conv_weight_h2(w[:, :c8].contiguous())
-                w16, i16 = ops.pack_conv_weight_h2(w[:, c8:c8 + c16].contiguous())
-                w32, i32 = ops.pack_conv_weight_h2(w[:, c8 + c16:].contiguous())
-                # the three partial sums share ONE BN scale: y16 / y32 are scaled by inv16 / inv8 and inv32 / inv8 so that
-                # the fused kernel can apply scale * inv8 to the sum (all factors are powers of two: exact)
-                return w8, w16, w32, (i16 / i8).contiguous(), (i32 / i8).contiguous(), (sc * i8).contiguous(), bi
-            w8, w16, w32, r16, r32, sc8, bi = self._h2cache.get(params, build_h2)
+            w8, w16, w32, r16, r32, sc8, bi = self.operands('h2', c8, c16)
             y16 = ops.conv3d_h2(as_h2(x16), w16, r16, ksize=1, out_h2=(False, False))
             y32 = ops.conv3d_h2(as_h2(x32), w32, r32, ksize=1, out_h2=(False, False))
             return ops.fpn3d_fuse(as_h2(x8), w8, y16, y32, sc8, bi, relu=True, out_h2=out_h2)
-
-        def build():
-            sc, bi = ops.fold_bn(cm.bn.weight, cm.bn.bias, cm.bn.running_mean, cm.bn.running_var,
-                                 cm.bn.eps)
-            return (ops.pack_conv_weight(w[:, :c8].contiguous()),
-                    ops.pack_conv_weight(w[:, c8:c8 + c16].contiguous()),
-                    ops.pack_conv_weight(w[:, c8 + c16:].contiguous()), sc, bi)
-        w8, w16, w32, sc, bi = self._cache.get(params, build)
+        w8, w16, w32, sc, bi = self.operands('f32', c8, c16)
         x8, x16, x32 = as_f32(x8), as_f32(x16), as_f32(x32)
         y16 = ops.conv3d_ndhwc(x16, w16, ksize=1)
         y32 = ops.conv3d_ndhwc(x32, w32, ksize=1)
@@ -718,49 +713,39 @@ class OccHead(nn.Module):
         for m in self.modules():
             if isinstance(m, nn.BatchNorm3d):
                 m.pw_sync = norm_cfg['type'] == 'SyncBN'
-        self._cache = _PackedCache()
+        self._derived = Derived()
 
-    def _folded(self, transposed=False, wino=False):
+    def _operands(self, kind):
+        """everything derived from the head's weights, both tap orders ([0] plain, [1] transposed) side by side.
+        'f32': (direct-MFMA conv weights [2], Winograd conv weights [2], s0, b0, w1, s1, b1, w2);
+        'h2' (ops.occ_head_h2): ((split-fp16 conv weight, s0 with the weight's pre-scale divided out) [2], b0, the packed
+        16->8->18 tail, its inverse pre-scale, the hidden layers' magnitude bounds)"""
         c0, bn0 = self.occ_convs[0][0], self.occ_convs[0][1]
         c1, bn1, c2 = self.occ_pred_conv[0], self.occ_pred_conv[1], self.occ_pred_conv[3]
-        params = [c0.weight, bn0.weight, bn0.bias, bn0.running_mean, bn0.running_var, c1.weight,
-                  bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var, c2.weight]
 
         def build():
             s0, b0 = ops.fold_bn(bn0.weight, bn0.bias, bn0.running_mean, bn0.running_var, bn0.eps)
             s1, b1 = ops.fold_bn(bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var, bn1.eps)
-            w0 = c0.weight
-            w0t = w0.permute(0, 1, 4, 3, 2).contiguous()
-            return ((ops.pack_conv_weight16(w0), ops.pack_conv_weight16(w0t)),
-                    (ops.pack_conv_weight_wino(w0, cout_total=16), ops.pack_conv_weight_wino(w0t, cout_total=16)),
-                    ops._pad32(s0, 1.0), ops._pad32(b0, 0.0),
-                    c1.weight.reshape(c1.weight.shape[0], -1).float().contiguous(), s1, b1,
-                    c2.weight.reshape(c2.weight.shape[0], -1).float().contiguous())
-        wpk, uwpk, s0, b0, w1, s1, b1, w2 = self._cache.get(params, build)
+            taps = (c0.weight, c0.weight.permute(0, 1, 4, 3, 2).contiguous())
+            w1 = c1.weight.reshape(c1.weight.shape[0], -1).float().contiguous()
+            w2 = c2.weight.reshape(c2.weight.shape[0], -1).float().contiguous()
+            if kind == 'f32':
+                return ([ops.pack_conv_weight16(w) for w in taps], [ops.pack_conv_weight_wino(w, cout_total=16) for w in taps],
+                        ops._pad32(s0, 1.0), ops._pad32(b0, 0.0), w1, s1, b1, w2)
+            packs = []
+            for w in taps:
+                wpk, inv = ops.pack_occ_weight_h2(w.float())
+                packs.append((wpk, (s0 * inv).contiguous()))
+            tailpk, inv2 = ops.pack_occ_tail_h2(w1, s1, b1, w2)
+            return packs, b0.contiguous(), tailpk, inv2, ops.occ_head_bounds(c0.weight, s0, b0, w1, s1, b1)
+        return self._derived.get(kind, (c0, bn0, c1, bn1, c2), build)
+
+    def _folded(self, transposed=False, wino=False):
+        wpk, uwpk, s0, b0, w1, s1, b1, w2 = self._operands('f32')
         return (uwpk if wino else wpk)[1 if transposed else 0], s0, b0, w1, s1, b1, w2
 
     def _folded_h2(self, transposed=False):
-        """operands of ops.occ_head_h2: split-fp16 conv weights (both tap orders), folded BN with the weights' pre-scale
-        divided out, the packed 16->8->18 tail"""
-        c0, bn0 = self.occ_convs[0][0], self.occ_convs[0][1]
-        c1, bn1, c2 = self.occ_pred_conv[0], self.occ_pred_conv[1], self.occ_pred_conv[3]
-        params = [c0.weight, bn0.weight, bn0.bias, bn0.running_mean, bn0.running_var, c1.weight,
-                  bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var, c2.weight]
-
-        def build():
-            s0, b0 = ops.fold_bn(bn0.weight, bn0.bias, bn0.running_mean, bn0.running_var, bn0.eps)
-            s1, b1 = ops.fold_bn(bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var, bn1.eps)
-            packs = []
-            for w in (c0.weight, c0.weight.permute(0, 1, 4, 3, 2).contiguous()):
-                wpk, inv = ops.pack_occ_weight_h2(w.float())
-                packs.append((wpk, (s0 * inv).contiguous()))
-            tailpk, inv2 = ops.pack_occ_tail_h2(c1.weight.reshape(c1.weight.shape[0], -1).float(), s1, b1,
-                                                c2.weight.reshape(c2.weight.shape[0], -1).float())
-            bounds = ops.occ_head_bounds(c0.weight, s0, b0, c1.weight.reshape(c1.weight.shape[0], -1), s1, b1)
-            return packs, b0.contiguous(), tailpk, inv2, bounds
-        if not hasattr(self, '_cache_h2'):
-            self._cache_h2 = _PackedCache()
-        packs, b0, tailpk, inv2, bounds = self._cache_h2.get(params, build)
+        packs, b0, tailpk, inv2, bounds = self._operands('h2')
         wpk, s0 = packs[1 if transposed else 0]
         return wpk, s0, b0, tailpk, inv2, bounds
 
@@ -817,13 +802,11 @@ class DownScaleModule3DCustom(nn.Module):
         self.downscale1 = nn.Conv3d(in_dim, in_dim * 2, 2, stride=2)
         self.downscale2 = nn.Conv3d(in_dim * 2, in_dim * 4, 2, stride=2)
         self.downscale3 = nn.Conv3d(in_dim * 4, in_dim * 4, 2, stride=2)
-        self._cache = _PackedCache()
+        self._derived = Derived()
 
     def _packed(self):
-        convs = (self.downscale1, self.downscale2, self.downscale3)
-        params = [c.weight for c in convs]
-        return self._cache.get(params, lambda: [ops.pack_conv_weight(c.weight.permute(0, 1, 4, 3, 2).contiguous())
-                                                for c in convs])
+        ws = (self.downscale1.weight, self.downscale2.weight, self.downscale3.weight)      # the biases go to the kernel live
+        return self._derived.get('f32', ws, lambda: [ops.pack_conv_weight(w.permute(0, 1, 4, 3, 2).contiguous()) for w in ws])
 
     def forward_cl(self, v_cl, want_levels=False):
         """v_cl (B,Z,Y,X,C) -> (B, 4*in_dim)."""
@@ -909,6 +892,7 @@ class NerfHead(nn.Module):
         else:
             self.class_weights = torch.ones(17) / 17
         self._t = None
+        self._derived = Derived()
 
     def t_table(self, device):
         """nerf_head.py:35-43, with the same torch calls (N_inner=391, N_outer=26 -> 417)."""
@@ -922,14 +906,11 @@ class NerfHead(nn.Module):
         return self._t
 
     def consts(self, bda, interval=0.5):
-        """the kernel's scalar arguments as host floats.  The registered buffers are read back ONCE per (device, in-place version): as
-        `float(v) for v in self.<buffer>` they were 24 one-element D2H syncs per rendered batch element (round 6)."""
+        """the kernel's scalar arguments as host floats.  The registered buffers are read back ONCE for as long as they stay what they
+        are (tensor_key): as `float(v) for v in self.<buffer>` they were 24 one-element D2H syncs per rendered batch element (round 6)."""
         bufs = (self.scene_center, self.scene_radius, self.xyz_min, self.xyz_max, self.act_shift)
-        key = tuple((b.device, b._version, b.data_ptr()) for b in bufs)
-        host = self.__dict__.get('_consts_host')
-        if host is None or host[0] != key:
-            host = self.__dict__['_consts_host'] = (key, [[float(v) for v in b.detach().cpu().reshape(-1)] for b in bufs])
-        sc, sr, xmin, xmax, shift = host[1]
+        sc, sr, xmin, xmax, shift = self._derived.get('consts', bufs,
+                                                      lambda: [[float(v) for v in b.cpu().reshape(-1)] for b in bufs])
         dist_thres = (2 + 2 * self.bg_len) / self.world_len * self.step_size * 0.95       # :197
         return sc + sr + [float(v) for v in bda.detach().cpu().reshape(-1)] + xmin + xmax + \
             [float(self.bg_len), shift[0], float(interval), float(dist_thres), float(self.fast_color_thres), float(self.radius)]

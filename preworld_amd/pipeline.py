@@ -580,9 +580,9 @@ class SampleStream:
 
     Every replay is range-checked before it counts (a miss: recalibrate, replay the same inputs, check again; still outside the
     window -> PreworldHipError).  Counters: `replays`, `recalibrations`, `recaptures`.
-    Stale captures: a fingerprint -- precision() and (data_ptr, _version) of every parameter and buffer -- is taken at capture and
-    compared at the start of every run(); a change (load_state_dict, an in-place update) re-captures.  Writes through `.data`
-    bypass the version counter and are NOT seen: call recapture() after them.
+    Stale captures: a fingerprint -- precision() and modules.tensor_key of every parameter and buffer -- is taken at capture and
+    compared at the start of every run(); a change (load_state_dict, an in-place update) re-captures.  In-place writes through
+    `.data` bypass the version counter and are NOT seen: call recapture() after them.
     close() frees the graphs and static buffers (about 1.5 GB per full-size C3 slot)."""
 
     def __init__(self, net, example_frames, example_ego=None, in_flight=2, n_steps=6, payload=True, score=None):
@@ -637,9 +637,8 @@ class SampleStream:
         self._capture()
 
     def _fingerprint(self):
-        from .modules import precision
-        ts = list(self.net.parameters()) + list(self.net.buffers())
-        return (precision(),) + tuple((t.data_ptr(), t._version) for t in ts)
+        from .modules import precision, tensor_key
+        return (precision(),) + tensor_key(list(self.net.parameters()) + list(self.net.buffers()))      # the net keeps them alive
 
     def _capture(self):
         self.close()
