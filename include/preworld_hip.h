@@ -26,6 +26,8 @@
  *   pw_cumdist_thres                    <- mmdet3d/models/nerf/cuda/ub360_utils.cpp:15-18
  *                                          (kernel ub360_utils_kernel.cu:13-47)
  *   pw_render_*                         <- mmdet3d/models/nerf/nerf_head.py:32-55,165-353
+ *   pw_optim_*                          <- torch/optim/adamw.py (adam.py _single_tensor_adam), torch/nn/utils/clip_grad.py
+ *                                          clip_grad_norm_, mmdet3d/core/hook/ema.py:48-59
  */
 #ifndef PREWORLD_HIP_H_
 #define PREWORLD_HIP_H_
@@ -784,6 +786,10 @@ int pw_upsample_trilinear_adjoint(const float* dhi, float* dlo, void* workspace,
 /* n device-to-device copies (src[i] -> dst[i], bytes[i] bytes; host arrays of device pointers) in one launch per 32 segments: a
  * sample's lifted inputs going into the static buffers of a captured step (preworld_amd.pipeline.CapturedSample.run). */
 int pw_copy_many(const void* const* src, void* const* dst, const size_t* bytes, int n, void* stream);
+
+/* The optimizer step (pw_optim_*: gradient norm, clipped AdamW, EMA) is declared in preworld_hip_optim.h, a part of this ABI kept
+ * in a file of its own. */
+#include "preworld_hip_optim.h"
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,7 @@ import torch      # before the library is loaded, see lib()
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PW_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libpreworld_hip.so')      # PW_LIB_PATH: A/B builds (tools/build_variant.py)
 HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip.h')
+OPTIM_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip_optim.h')      # the part preworld_hip.h includes (pw_optim_*)
 
 _CTYPES = {
     'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64,
@@ -146,6 +147,8 @@ def parse_header(path=HEADER_PATH):
 
 
 _protos, PW = _parse(HEADER_PATH)       # PW: the header's integer `#define PW_*` values by name
+_optim_protos, PW_OPTIM = _parse(OPTIM_HEADER_PATH)        # ... and those of the optimizer part (PW_OPTIM_*)
+_protos.update(_optim_protos)
 _lib = None
 _fns = {}
 

@@ -30,6 +30,9 @@ EXTRA = {
     'pw_depth_sup.hip': ['-ffp-contract=off'],
     # (px - mean) * stdinv must stay a subtract and a multiply: the float output is pinned bit for bit
     'pw_image_prep.hip': ['-ffp-contract=off'],
+    # the fp32 AdamW / EMA update is the written sequence of roundings (torch's op order, restated in tests/_optim_ref64.py): a fused
+    # p * (1 - lr wd) or addcdiv would stay inside any tolerance and no longer be that sequence
+    'pw_optim.hip': ['-ffp-contract=off'],
 }
 
 
@@ -38,12 +41,12 @@ def sources():
 
 
 def source_hash():
-    """sha256[:16] over every kernel source, kernel header and the C ABI header (names + contents, sorted): what
+    """sha256[:16] over every kernel source, kernel header and the C ABI headers (names + contents, sorted): what
     pw_build_id() of a library built from this tree returns"""
     import hashlib
     h = hashlib.sha256()
     files = sorted(f for f in os.listdir(CSRC) if f.endswith(('.hip', '.h')))
-    for f in files + [os.path.join('..', '..', 'include', 'preworld_hip.h')]:
+    for f in files + [os.path.join('..', '..', 'include', h) for h in ('preworld_hip.h', 'preworld_hip_optim.h')]:
         h.update(os.path.basename(f).encode() + b'\0')
         h.update(open(os.path.join(CSRC, f), 'rb').read())
     return h.hexdigest()[:16]
@@ -70,7 +73,7 @@ def _compile(src, force, verbose):
                                         if h.endswith('.h')]
     if src == 'pw_core.hip':
         deps.append(os.path.join(CSRC, 'pw_build_id.inc'))
-    deps.append(os.path.join(HERE, '..', 'include', 'preworld_hip.h'))
+    deps += [os.path.join(HERE, '..', 'include', h) for h in ('preworld_hip.h', 'preworld_hip_optim.h')]
     if not force and not _needs_build(obj, deps):
         return obj, False
     cmd = ['hipcc'] + COMMON + EXTRA.get(src, []) + ['-c', os.path.join(CSRC, src), '-o', obj]

@@ -1813,3 +1813,37 @@ def prepare_images(src_u8, plan, out=None, canvas=None):
               int(plan.any_rot), plan.ws, out, canvas, ctypes.byref(n), _lib.STREAM)
     plan.launches = n.value
     return out
+
+
+# ------------------------------------------------------------------------------ the optimizer step (preworld_amd/optim.py)
+OPTIM_LAUNCHES = {'sqnorm': 0, 'update': 0}       # kernel launches the two wrappers below enqueued (tests count them)
+
+
+def optim_plan(p, g, m, v, e, weight_decay, lr_mul, group):
+    """Lay out the device plan of pw_optim_sqnorm / pw_optim_update for rows of fp32 device tensors: p[i] with g / m / v [i] all
+    tensors (an optimizer row) or all None (an EMA-only row), e[i] the shadow or None.  Returns (plan_host, n_chunks): a pinned
+    int64 host tensor for ONE asynchronous copy to the device, and the chunk count.  Nothing is dereferenced or launched."""
+    n = len(p)
+    numel = torch.tensor([t.numel() for t in p], dtype=torch.int64)
+    tabs = [_lib.table(x) for x in (p, g, m, v, e)]
+    nbytes = _lib.call_size('pw_optim_plan_bytes', n, numel, *tabs)
+    if nbytes < 0:
+        raise _lib.PreworldHipError('pw_optim_plan_bytes failed: %s' % _lib.lib().pw_last_error().decode())
+    plan = torch.empty(nbytes // 8, dtype=torch.int64, pin_memory=torch.cuda.is_available())
+    n_chunks = torch.zeros(1, dtype=torch.int64)
+    _lib.call('pw_optim_plan_layout', n, numel, *tabs, torch.tensor(weight_decay, dtype=torch.float64).reshape(n),
+              torch.tensor(lr_mul, dtype=torch.float64).reshape(n), torch.tensor(group, dtype=_i32).reshape(n), plan, nbytes, n_chunks)
+    return plan, int(n_chunks[0])
+
+
+def optim_sqnorm(plan, n_rows, n_chunks, slab):
+    """launch 1: per-block partial sums of g*g in double into slab (clip_grad_norm_'s norm, first half)"""
+    _lib.call('pw_optim_sqnorm', plan, plan.numel() * 8, n_rows, n_chunks, slab, _lib.STREAM)
+    OPTIM_LAUNCHES['sqnorm'] += 1
+
+
+def optim_update(plan, n_rows, n_chunks, hyper, n_groups, slab, ctr, ema_updates, norm_out, use_norm, clip, use_ema, skip_nonfinite):
+    """launch 2: the clipped AdamW update (torch/optim/adam.py single-tensor path) and ModelEMA.update's blend (core/hook/ema.py:48-59)"""
+    _lib.call('pw_optim_update', plan, plan.numel() * 8, n_rows, n_chunks, hyper, n_groups, slab, int(use_norm), int(clip),
+              int(use_ema), int(skip_nonfinite), ctr, ema_updates, norm_out, _lib.STREAM)
+    OPTIM_LAUNCHES['update'] += 1
