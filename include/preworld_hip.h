@@ -791,6 +791,10 @@ int pw_copy_many(const void* const* src, void* const* dst, const size_t* bytes, 
  * in a file of its own. */
 #include "preworld_hip_optim.h"
 
+/* The pre-train ray supervision (pw_ray_*: lidar sweeps + lidarseg bytes + uint8 frames -> ray table and sampling weights) is
+ * declared in preworld_hip_rays.h, a part of this ABI kept in a file of its own for the same reason. */
+#include "preworld_hip_rays.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PW_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libpreworld_hip.so')      # PW_LIB_PATH: A/B builds (tools/build_variant.py)
 HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip.h')
 OPTIM_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip_optim.h')      # the part preworld_hip.h includes (pw_optim_*)
+RAYS_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip_rays.h')        # ... and the ray-supervision part (pw_ray_*)
 
 _CTYPES = {
     'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64,
@@ -149,6 +150,8 @@ def parse_header(path=HEADER_PATH):
 _protos, PW = _parse(HEADER_PATH)       # PW: the header's integer `#define PW_*` values by name
 _optim_protos, PW_OPTIM = _parse(OPTIM_HEADER_PATH)        # ... and those of the optimizer part (PW_OPTIM_*)
 _protos.update(_optim_protos)
+_rays_protos, PW_RAYS = _parse(RAYS_HEADER_PATH)           # ... and those of the ray-supervision part (PW_RAY_*)
+_protos.update(_rays_protos)
 _lib = None
 _fns = {}
 

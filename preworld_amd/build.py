@@ -33,6 +33,9 @@ EXTRA = {
     # the fp32 AdamW / EMA update is the written sequence of roundings (torch's op order, restated in tests/_optim_ref64.py): a fused
     # p * (1 - lr wd) or addcdiv would stay inside any tolerance and no longer be that sequence
     'pw_optim.hip': ['-ffp-contract=off'],
+    # the projection of a lidar point is a written sequence of float32 / float64 roundings (tests/_ray_labels_np.py): it decides
+    # which pixel a point lands in and whether it is kept
+    'pw_ray_labels.hip': ['-ffp-contract=off'],
 }
 
 
@@ -46,7 +49,7 @@ def source_hash():
     import hashlib
     h = hashlib.sha256()
     files = sorted(f for f in os.listdir(CSRC) if f.endswith(('.hip', '.h')))
-    for f in files + [os.path.join('..', '..', 'include', h) for h in ('preworld_hip.h', 'preworld_hip_optim.h')]:
+    for f in files + [os.path.join('..', '..', 'include', h) for h in ('preworld_hip.h', 'preworld_hip_optim.h', 'preworld_hip_rays.h')]:
         h.update(os.path.basename(f).encode() + b'\0')
         h.update(open(os.path.join(CSRC, f), 'rb').read())
     return h.hexdigest()[:16]
@@ -73,7 +76,7 @@ def _compile(src, force, verbose):
                                         if h.endswith('.h')]
     if src == 'pw_core.hip':
         deps.append(os.path.join(CSRC, 'pw_build_id.inc'))
-    deps += [os.path.join(HERE, '..', 'include', h) for h in ('preworld_hip.h', 'preworld_hip_optim.h')]
+    deps += [os.path.join(HERE, '..', 'include', h) for h in ('preworld_hip.h', 'preworld_hip_optim.h', 'preworld_hip_rays.h')]
     if not force and not _needs_build(obj, deps):
         return obj, False
     cmd = ['hipcc'] + COMMON + EXTRA.get(src, []) + ['-c', os.path.join(CSRC, src), '-o', obj]

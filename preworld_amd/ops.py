@@ -1087,6 +1087,218 @@ def depth_bce(pred, labels, weight):
     return DepthBCE.apply(pred, labels, weight)
 
 
+# ------------------------------------------------------------------------------ ray supervision from the sweep
+RAY_MEAN_STD = (0.485, 0.456, 0.406, 0.229, 0.224, 0.225)       # transforms.Normalize of nuscenes_dataset_occ.py:133-140
+RAY_POSE_DOUBLES = _lib.PW_RAYS['PW_RAY_POSE_DOUBLES']
+_RAY_BLOCK = 256
+
+
+class RaySweeps:
+    """The T sweeps of a sample as the kernels take them: points (T, Pmax, C) float32, labels (T, Pmax) uint8, n_pts int32 (T)
+    on the device (None: every row counts), view_pose (T N, 57) float64 (transforms.compose_view_poses), lut uint8 (256).
+    `points` / `point_labels` may be lists of T per-sweep tensors (padded here, lengths known on the host: one small copy,
+    nothing read back) or the padded tensors themselves with `n_pts`."""
+
+    def __init__(self, points, point_labels, view_pose, label_lut=None, n_pts=None):
+        if isinstance(points, (list, tuple)):
+            dev = points[0].device
+            T, C = len(points), int(points[0].shape[1])
+            lens = [int(p.shape[0]) for p in points]
+            Pmax = max(1, max(lens))
+            if len(point_labels) != T or any(int(l.numel()) != n for l, n in zip(point_labels, lens)):
+                raise _lib.PreworldHipError('point_labels must hold one uint8 label per point of every sweep')
+            pts = torch.zeros(T, Pmax, C, device=dev, dtype=_f32)
+            lab = torch.zeros(T, Pmax, device=dev, dtype=torch.uint8)
+            for t in range(T):
+                pts[t, :lens[t]] = points[t]
+                lab[t, :lens[t]] = point_labels[t].view(-1)
+            if n_pts is None and any(n != Pmax for n in lens):
+                n_pts = torch.tensor(lens, dtype=_i32).to(dev, non_blocking=True)
+            points, point_labels = pts, lab
+        if points.dim() != 3 or points.shape[2] < 3 or points.shape[1] < 1:
+            raise _lib.PreworldHipError('points must be (T, Pmax >= 1, >= 3), got %s' % (tuple(points.shape),))
+        T, Pmax = int(points.shape[0]), int(points.shape[1])
+        if point_labels.dtype != torch.uint8 or tuple(point_labels.shape) != (T, Pmax):
+            raise _lib.PreworldHipError('point_labels must be uint8 (T, Pmax) = (%d, %d), got %s %s' %
+                                        (T, Pmax, point_labels.dtype, tuple(point_labels.shape)))
+        if n_pts is not None and (n_pts.dtype != _i32 or n_pts.numel() != T):
+            raise _lib.PreworldHipError('n_pts must be int32 with T = %d entries' % T)
+        V = int(view_pose.shape[0])
+        if view_pose.dim() != 2 or view_pose.shape[1] != RAY_POSE_DOUBLES or V % T:
+            raise _lib.PreworldHipError('view_pose must be (T N, %d), got %s for T = %d' % (RAY_POSE_DOUBLES, tuple(view_pose.shape), T))
+        dev = points.device
+        self.points, self.labels, self.n_pts = points.float().contiguous(), point_labels.contiguous(), n_pts
+        self.pose = view_pose.to(device=dev, dtype=torch.float64).contiguous()
+        if label_lut is None:
+            label_lut = torch.arange(256, dtype=torch.uint8)
+        label_lut = torch.as_tensor(label_lut)
+        if label_lut.numel() != 256:
+            raise _lib.PreworldHipError('label_lut must have 256 entries')
+        self.lut = label_lut.to(device=dev, dtype=torch.uint8).contiguous()
+        self.T, self.N, self.V, self.Pmax = T, V // T, V, Pmax
+        self.nblk = -(-Pmax // _RAY_BLOCK)
+
+    def head(self):
+        return (self.points, self.points.shape[2])
+
+    def count(self, H, W, owners=True):
+        """project (+ owners) + scan -> (slots, block_base, view_off); view_off[V] is the number of rows, on the device.
+        owners=False: no owner table is allocated, cleared or filled (slots None): what stage A alone needs"""
+        dev = self.points.device
+        slots = torch.empty(ray_slot_count(self.V * self.Pmax), device=dev, dtype=torch.int64) if owners else None
+        block_base = torch.empty(self.V * self.nblk, device=dev, dtype=_i32)
+        view_off = torch.empty(self.V + 1, device=dev, dtype=_i32)
+        _lib.call('pw_ray_sweep_count', self.points, self.points.shape[2], self.n_pts, self.T, self.N, self.Pmax, self.pose, H, W,
+                  slots, slots.numel() if owners else 0, block_base, view_off, _lib.STREAM)
+        return slots, block_base, view_off
+
+
+def ray_slot_count(n_items):
+    """entries of the owner table for n_items insertions: the power of two >= 2 n_items (load <= 1/2), at least 1024"""
+    n = 1024
+    while n < 2 * n_items:
+        n *= 2
+    return n
+
+
+def ray_scratch_bytes(T, N, Pmax):
+    """device scratch of one sweeps-mode table: owner slots + block bases + view offsets"""
+    V = T * N
+    return 8 * ray_slot_count(V * Pmax) + 4 * V * (-(-Pmax // _RAY_BLOCK)) + 4 * (V + 1)
+
+
+def _ray_frames(frames_u8, view_frame, V, H, W):
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or tuple(frames_u8.shape[1:]) != (H, W, 3):
+        raise _lib.PreworldHipError('frames_u8 must be uint8 (F, %d, %d, 3), got %s %s' % (H, W, frames_u8.dtype, tuple(frames_u8.shape)))
+    if any(s < 0 for s in frames_u8.stride()):
+        raise _lib.PreworldHipError('frames_u8 must not have negative strides')
+    F = int(frames_u8.shape[0])
+    if view_frame is None:
+        if F < V:
+            raise _lib.PreworldHipError('%d frames for %d views: pass view_frame' % (F, V))
+    else:
+        if isinstance(view_frame, torch.Tensor):
+            if view_frame.dtype != _i32 or view_frame.numel() != V:
+                raise _lib.PreworldHipError('view_frame must be int32 with V = %d entries' % V)
+        else:
+            idx = [int(i) for i in view_frame]
+            if len(idx) != V or min(idx) < 0 or max(idx) >= F:
+                raise _lib.PreworldHipError('view_frame must name one of the %d frames for each of the %d views' % (F, V))
+            view_frame = torch.tensor(idx, dtype=_i32).to(frames_u8.device, non_blocking=True)
+    return (_lib.strided(frames_u8),) + tuple(int(s) for s in frames_u8.stride()) + (F, view_frame)
+
+
+def _ray_cams(c2w, K, V, dev):
+    c2w = torch.as_tensor(c2w).to(device=dev, dtype=_f32).contiguous()
+    K = torch.as_tensor(K).to(device=dev, dtype=_f32).contiguous()
+    if tuple(c2w.shape) != (V, 4, 4) or tuple(K.shape) != (V, 3, 3):
+        raise _lib.PreworldHipError('c2w must be (V,4,4) and K (V,3,3) with V = %d, got %s %s' % (V, tuple(c2w.shape), tuple(K.shape)))
+    return c2w, K
+
+
+def _ray_out(out, cap, dev):
+    if out is None:
+        return torch.empty(max(cap, 1), 16, device=dev, dtype=_f32)
+    if out.dtype != _f32 or tuple(out.shape) != (cap, 16) or cap < 1 or not out.is_contiguous() or out.data_ptr() % 16:
+        raise _lib.PreworldHipError('out must be a contiguous, 16-byte aligned float32 (capacity, 16) = (%d, 16) buffer' % cap)
+    return out
+
+
+def sweep_pixel_labels(points, point_labels, view_pose, image_hw, label_lut=None, n_pts=None):
+    """Stage A alone: tools/gen_data/gen_depth_gt.py and gen_seg_gt_from_lidarseg.py for every sweep and camera of a sample.
+    -> (depth_list (R,3) float32 rows (u, v, depth), seg_list (R,3) rows (u, v, class), view_off int32 (V+1)): rows
+    view_off[v] .. view_off[v+1]-1 are, byte for byte, the contents of the two .bin files of view v = t N + camera.  Reads the
+    row count back (one host synchronisation)."""
+    sw = points if isinstance(points, RaySweeps) else RaySweeps(points, point_labels, view_pose, label_lut, n_pts)
+    H, W = int(image_hw[0]), int(image_hw[1])
+    _, block_base, view_off = sw.count(H, W, owners=False)
+    R = int(view_off[-1].item())
+    dev = sw.points.device
+    depth_list = torch.empty(max(R, 1), 3, device=dev, dtype=_f32)
+    seg_list = torch.empty(max(R, 1), 3, device=dev, dtype=_f32)
+    _lib.call('pw_ray_sweep_lists', *sw.head(), sw.labels, sw.n_pts, sw.T, sw.N, sw.Pmax, sw.lut, sw.pose, H, W, block_base,
+              max(R, 1), depth_list, seg_list, _lib.STREAM)
+    return depth_list[:R], seg_list[:R], view_off
+
+
+def ray_table(c2w, K, frames_u8, sweeps=None, lists=None, view_frame=None, capacity=None, n_cls=17, mean_std=RAY_MEAN_STD, out=None):
+    """The (R,16) ray table of nuscenes_dataset_occ.py:197-270 get_rays + ray.py:47-56 for all V views of a sample.
+      sweeps = RaySweeps(...)                               -- from the raw sweeps (stage A and B), or
+      lists = (depth_list (n,3), seg_list (n,3), view_off)  -- from the contents of the two gen tools' files, views back to back
+                                                               (view_off int32 (V+1) on the device or a host sequence)
+    c2w (V,4,4) = sensor2keyego, K (V,3,3); frames_u8 uint8 (F,H,W,3) with any strides, view_frame[v] the frame of view v
+    (default v).  -> (rays (capacity,16), view_off (V+1) int32 on the device, counts int64 (n_cls) of the rows written).
+    view_off[V] = R is the number of kept points; rows >= capacity are dropped, rows between R and capacity are not written
+    (ray_table_weights zeroes them).  capacity=None: R is read back (one host synchronisation) and capacity = R.  out: the
+    caller's own (capacity,16) float32 buffer."""
+    if (sweeps is None) == (lists is None):
+        raise _lib.PreworldHipError('ray_table takes either sweeps= or lists=')
+    H, W = int(frames_u8.shape[1]), int(frames_u8.shape[2])
+    dev = frames_u8.device
+    ms = (ctypes.c_float * 6)(*[float(v) for v in mean_std])
+    counts = torch.zeros(n_cls, device=dev, dtype=torch.int64)
+    if sweeps is not None:
+        sw = sweeps
+        c2w, K = _ray_cams(c2w, K, sw.V, dev)
+        fr = _ray_frames(frames_u8, view_frame, sw.V, H, W)
+        slots, block_base, view_off = sw.count(H, W)
+        cap = int(view_off[-1].item()) if capacity is None else int(capacity)
+        rays = _ray_out(out, cap, dev)
+        _lib.call('pw_ray_sweep_table', *sw.head(), sw.labels, sw.n_pts, sw.T, sw.N, sw.Pmax, sw.lut, sw.pose, H, W, slots,
+                  slots.numel(), block_base, *fr, ms, c2w, K, max(cap, 1), rays, n_cls, counts, _lib.STREAM)
+        return rays[:cap], view_off, counts
+    depth_list, seg_list, view_off = lists
+    depth_list, seg_list = depth_list.float().contiguous(), seg_list.float().contiguous()
+    n = int(depth_list.shape[0])
+    if depth_list.dim() != 2 or depth_list.shape[1] != 3 or tuple(seg_list.shape) != (n, 3):
+        raise _lib.PreworldHipError('depth_list and seg_list must both be (n, 3), got %s %s' % (tuple(depth_list.shape), tuple(seg_list.shape)))
+    if not isinstance(view_off, torch.Tensor):
+        off = [int(v) for v in view_off]
+        if off[0] != 0 or off[-1] != n or any(a > b for a, b in zip(off, off[1:])):
+            raise _lib.PreworldHipError('view_off must rise from 0 to n = %d' % n)
+        view_off = torch.tensor(off, dtype=_i32).to(dev, non_blocking=True)
+    if view_off.dtype != _i32 or view_off.dim() != 1 or view_off.numel() < 2:
+        raise _lib.PreworldHipError('view_off must be int32 (V + 1)')
+    V = view_off.numel() - 1
+    c2w, K = _ray_cams(c2w, K, V, dev)
+    fr = _ray_frames(frames_u8, view_frame, V, H, W)
+    cap = n if capacity is None else int(capacity)
+    rays = _ray_out(out, cap, dev)
+    if n > 0:
+        slots = torch.empty(ray_slot_count(n), device=dev, dtype=torch.int64)
+        _lib.call('pw_ray_lists_table', depth_list, seg_list, n, view_off, V, H, W, slots, slots.numel(), *fr, ms, c2w, K,
+                  max(cap, 1), rays, n_cls, counts, _lib.STREAM)
+    return rays[:cap], view_off, counts
+
+
+def ray_table_weights(rays, view_off, frame_ids, dynamic_class=None, balance_weight=None, counts=None, weight_adj=0.3,
+                      weight_dyn=0.0, n_cls=17):
+    """ray.py:93-112 over the whole table in one launch: rays (capacity,16) and view_off, counts of ray_table; frame_ids[v] the
+    frame id of view v (0 = key frame).  balance_weight (n_cls) float32, or None for the batch statistics from `counts`.
+    Rows >= view_off[V] get weight 0 (torch.multinomial never draws them) and are zeroed."""
+    cap = int(rays.shape[0])
+    dev = rays.device
+    w = torch.empty(cap, device=dev, dtype=_f32)
+    if cap == 0:
+        return w
+    V = view_off.numel() - 1
+    if not isinstance(frame_ids, torch.Tensor):
+        frame_ids = torch.tensor([int(f) for f in frame_ids], dtype=_i32).to(dev, non_blocking=True)
+    if frame_ids.dtype != _i32 or frame_ids.numel() != V:
+        raise _lib.PreworldHipError('frame_ids must be int32 with V = %d entries' % V)
+    if dynamic_class is None:
+        dynamic_class = torch.zeros(0, dtype=_i32)
+    dyn = torch.as_tensor(dynamic_class).to(device=dev, dtype=_i32).contiguous()
+    if balance_weight is not None:
+        balance_weight = torch.as_tensor(balance_weight).to(device=dev, dtype=_f32).contiguous()
+        n_cls = balance_weight.numel()
+    elif counts is None or counts.numel() != n_cls:
+        raise _lib.PreworldHipError('ray_table_weights needs balance_weight or the int64 counts of ray_table')
+    _lib.call('pw_ray_table_weights', rays, cap, view_off, V, frame_ids, balance_weight, counts, n_cls,
+              dyn if dyn.numel() else None, dyn.numel(), float(weight_adj), float(weight_dyn), w, _lib.STREAM)
+    return w
+
+
 # ------------------------------------------------------------------------------ DepthNet tail
 def depthnet_tail(x, D, C):
     """x (BN, >=D+C, H, W) DepthNet output -> (depth (BN,D,H,W) softmaxed over D,

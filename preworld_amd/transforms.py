@@ -13,7 +13,11 @@ cannot always separate two depths of one pixel ("Depth supervisi
 
 `PrepareImageInputs` / `PrepareImageInputs4DTraj` (loading.py:902-1140, loading_traj_temporal.py:230-577) are here too: camera
 frames -> the network's `img_inputs`, with resize / crop / flip / rotate / normalise on the device (ops.prepare_images,
-csrc/pw_image_prep.hip); `transforms.register_image_pipelines(PIPELINES)` (INTEGRATION.md, "Camera frames to network input")."""
+csrc/pw_image_prep.hip); `transforms.register_image_pipelines(PIPELINES)` (INTEGRATION.md, "Camera frames to network input").
+
+`SweepsToRays` is the pre-train twin of PointToMultiViewDepth: sweeps with their lidarseg bytes + the staged frames -> the ray
+table of the reference's `get_rays` (ops.ray_table, csrc/pw_ray_labels.hip); `transforms.register_ray_pipelines(PIPELINES)`
+(INTEGRATION.md, "Ray supervision from the sweep")."""
 import numpy as np
 import torch
 
@@ -55,6 +59,110 @@ def compose_lidar2img(curr, cam_names, intrins):
         K[:3, :3] = torch.as_tensor(intrins[i], dtype=torch.float32).cpu()
         out.append(K @ (torch.inverse(cam2global) @ lidar2global))
     return torch.stack(out)
+
+
+def compose_view_poses(infos, cam_names):
+    """Stage A's poses (tools/gen_data/gen_depth_gt.py:17-52, map_pointcloud_to_image) for every sweep of `infos` and every
+    camera of that sweep's own sample: (T N, 57) float64 rows R1 t1 (lidar->ego), R2 t2 (ego->global), -t3 R3^T (global->camera
+    ego), -t4 R4^T (camera ego->camera), K -- rotations from the quaternions in float64, nothing rounded here (the kernel
+    rounds the translations to float32 as the devkit's float32 cloud does).  View v = t N + camera."""
+    rows = []
+    for info in infos:
+        for name in cam_names:
+            cam = info['cams'][name]
+            rows.append(np.concatenate([
+                quaternion_rotation_matrix(info['lidar2ego_rotation']).ravel(), np.asarray(info['lidar2ego_translation'], np.float64),
+                quaternion_rotation_matrix(info['ego2global_rotation']).ravel(), np.asarray(info['ego2global_translation'], np.float64),
+                -np.asarray(cam['ego2global_translation'], np.float64), quaternion_rotation_matrix(cam['ego2global_rotation']).T.ravel(),
+                -np.asarray(cam['sensor2ego_translation'], np.float64), quaternion_rotation_matrix(cam['sensor2ego_rotation']).T.ravel(),
+                np.asarray(cam['cam_intrinsic'], np.float64).ravel()]))
+    return torch.from_numpy(np.stack(rows))
+
+
+def compose_sensor2keyegos(infos, cam_names):
+    """nuscenes_dataset_occ.py:248-259: sensor2keyego = inverse(keyego2global) @ ego2global @ sensor2ego per view, the float32
+    poses multiplied in float64 and rounded to float32; keyego2global is the same camera's ego pose in the first (key) frame.
+    infos: the frames in [0] + aux_frames order.  Returns (T N, 4, 4) float32 on the host."""
+    s2e = torch.stack([_pose(info['cams'][n]['sensor2ego_rotation'], info['cams'][n]['sensor2ego_translation'])
+                       for info in infos for n in cam_names]).view(len(infos), len(cam_names), 4, 4)
+    e2g = torch.stack([_pose(info['cams'][n]['ego2global_rotation'], info['cams'][n]['ego2global_translation'])
+                       for info in infos for n in cam_names]).view(len(infos), len(cam_names), 4, 4)
+    global2keyego = torch.inverse(e2g[0:1].double())
+    return (global2keyego @ e2g.double() @ s2e.double()).float().view(-1, 4, 4)
+
+
+class SweepsToRays(object):
+    """The ray supervision of the pre-train dataloader (nuscenes_dataset_occ.py:197-270, get_rays) as a pipeline step, from what
+    a training run already has on the device: no gen_depth_gt / gen_seg_gt_from_lidarseg directories, no per-camera loop
+    (ops.ray_table, csrc/pw_ray_labels.hip).  Sits beside PointToMultiViewDepth.
+
+    Reads results['curr'] (the key sample's info dict: scene_token, lidar2ego_*, ego2global_*, cams) and results['ray_frames'],
+    {frame id: dict(info=..., points=(P, >= 3) tensor or object with .tensor, point_labels=uint8 (P) lidarseg bytes, frames=
+    uint8 (N, H, W, 3) tensor)} for frame ids [0] + aux_frames; or, with results['ray_staged'] = the staged uint8 (M, H, W, 3)
+    buffer of PrepareImageInputs4DTraj, frame_index=[N indices into it] in place of frames= (nothing is copied then).  Frames are picked
+    as get_rays picks them: a neighbour that is missing or belongs to another scene falls back to the key sample (entry 0).
+    Writes results['rays']: (R, 16), or (max_ray_nums, 16) drawn by weight when R is larger; with capacity= set,
+    (table, weights, n_rows) without synchronising (rays.generate_rays_from_sweeps).
+
+    label_lut (256 entries, lidarseg byte -> class), dynamic_class (the classes weighted by weight_dyn in the auxiliary frames; None:
+    none, as in rays.generate_rays) and class_nums (the dataset-level ray counts per class, from which the
+    balance weights exp(0.005 (max / n - 1)) are made; None or wrs_use_batch: the batch's own counts) are the caller's.
+    The process rules of PointToMultiViewDepth hold: no forked workers."""
+
+    def __init__(self, aux_frames=(-1, 1), max_ray_nums=0, wrs_use_batch=False, class_nums=None, dynamic_class=None,
+                 label_lut=None, weight_adj=0.3, weight_dyn=0.0, capacity=None, device='cuda'):
+        self.aux_frames = list(aux_frames)
+        self.max_ray_nums = max_ray_nums
+        self.balance_weight = None
+        if not wrs_use_batch and class_nums is not None:
+            n = torch.as_tensor(class_nums, dtype=torch.float32)
+            self.balance_weight = torch.exp(0.005 * (n.max() / n - 1))
+        self.dynamic_class = None if dynamic_class is None else torch.tensor(list(dynamic_class), dtype=torch.int32)
+        self.label_lut = label_lut
+        self.weight_adj, self.weight_dyn, self.capacity, self.device = weight_adj, weight_dyn, capacity, device
+
+    def pick_frames(self, results):
+        """-> ([frame ids], [the entry used for each]) in [0] + aux_frames order"""
+        key = results['ray_frames'][0]
+        scene = results['curr']['scene_token']
+        ids, picked = [0] + self.aux_frames, []
+        for time_id in ids:
+            entry = results['ray_frames'].get(time_id)
+            if entry is None or entry['info']['scene_token'] != scene:
+                entry = key                                # out of sequence
+            picked.append(entry)
+        return ids, picked
+
+    def __call__(self, results):
+        from . import rays
+        dev = torch.device(self.device)
+        ids, picked = self.pick_frames(results)
+        cam_names = list(picked[0]['info']['cams'].keys())
+        infos = [e['info'] for e in picked]
+        N = len(cam_names)
+        points = [(e['points'].tensor if hasattr(e['points'], 'tensor') else e['points']).to(dev) for e in picked]
+        labels = [torch.as_tensor(e['point_labels']).to(dev) for e in picked]
+        if 'ray_staged' in results:                        # the staged buffer of PrepareImageInputs4DTraj + indices into it: no copy
+            frames = results['ray_staged'].to(dev)
+            view_frame = [int(i) for e in picked for i in e['frame_index']]
+        else:                                              # one (N,H,W,3) tensor per frame: each distinct one once
+            uniq = []
+            for e in picked:
+                if not any(e is u for u in uniq):
+                    uniq.append(e)
+            frames = uniq[0]['frames'].to(dev) if len(uniq) == 1 else torch.cat([u['frames'].to(dev) for u in uniq], 0)
+            view_frame = [[e is u for u in uniq].index(True) * N + c for e in picked for c in range(N)]
+        intrins = torch.tensor([info['cams'][n]['cam_intrinsic'] for info in infos for n in cam_names], dtype=torch.float32)
+        time_ids = {t: list(range(k * N, (k + 1) * N)) for k, t in enumerate(ids)}
+        results['rays'] = rays.generate_rays_from_sweeps(
+            points, labels, frames, compose_view_poses(infos, cam_names), compose_sensor2keyegos(infos, cam_names), intrins,
+            max_ray_nums=self.max_ray_nums, time_ids=time_ids, dynamic_class=self.dynamic_class, balance_weight=self.balance_weight,
+            weight_adj=self.weight_adj, weight_dyn=self.weight_dyn, label_lut=self.label_lut, capacity=self.capacity,
+            view_frame=view_frame)
+        return results
+
+    def __repr__(self):
+        return '%s(aux_frames=%r, max_ray_nums=%r, capacity=%r)' % (type(self).__name__, self.aux_frames, self.max_ray_nums, self.capacity)
 
 
 class PointToMultiViewDepth(object):
@@ -317,6 +425,13 @@ def register_pipelines(registry):
     under the reference's name, replacing the reference class.  Returns the registered names."""
     registry.register_module(name='PointToMultiViewDepth', force=True, module=PointToMultiViewDepth)
     return ['PointToMultiViewDepth']
+
+
+def register_ray_pipelines(registry):
+    """Put SweepsToRays into an mmcv-style pipeline registry.  The reference has no pipeline class of this name (its dataset
+    builds the rays in get_rays), so nothing is replaced.  Returns the registered names."""
+    registry.register_module(name='SweepsToRays', force=True, module=SweepsToRays)
+    return ['SweepsToRays']
 
 
 def register_image_pipelines(registry):

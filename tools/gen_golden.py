@@ -476,6 +476,101 @@ def gen_rays():
          balance_weight=bw.numpy(), weights_given=captured['w'].numpy())
 
 
+def gen_ray_labels():
+    """Stage B of the ray supervision ("Ray supervision from the sweep"): the reference's OWN get_rays
+    (mmdet3d/datasets/nuscenes_dataset_occ.py:197-270 with its load_depth / load_seg_label / load_img / get_sensor_transforms and
+    ray.py's generate_rays) run on the .bin files that tests/_ray_labels_np.py's stage A writes for a synthetic two-frame,
+    two-camera sample -- the dataset module is loaded under the shim (pyquaternion's Quaternion and torchvision's ToTensor /
+    Normalize are stood in for: transforms.quaternion_rotation_matrix, and permute + (x - mean) / std in float32; load_img's
+    array conversion is respelled for NumPy 2), get_rays is
+    called unbound on a plain object carrying the attributes it reads.  The frames go through lossless PNG files.  The sampler
+    weights are captured as gen_rays does."""
+    import tempfile
+    from PIL import Image
+    sys.path.insert(0, os.path.join(REPO, 'tests'))
+    import _ray_labels_np as RN
+    from preworld_amd import transforms as TF
+
+    class Quaternion:
+        def __init__(self, *q):
+            self.rotation_matrix = TF.quaternion_rotation_matrix(q[0] if len(q) == 1 else q)
+    _mod('pyquaternion', Quaternion=Quaternion)
+    _mod('tqdm', tqdm=lambda x, *a, **k: x)
+    _mod('PIL', Image=Image) if 'PIL' not in sys.modules else None
+    mean, std = torch.tensor([0.485, 0.456, 0.406]), torch.tensor([0.229, 0.224, 0.225])
+    tvt = _mod('torchvision.transforms', Compose=None, ToTensor=None, Normalize=None)
+    _mod('torchvision', transforms=tvt)
+    _mod('mmdet3d.datasets')
+    _mod('mmdet3d.datasets.builder', DATASETS=_REG)
+    _mod('mmdet3d.datasets.nuscenes_dataset', NuScenesDataset=object)
+    _mod('mmdet3d.datasets.occ_metrics', Metric_mIoU=None, Metric_FScore=None)
+    ray = load_ref('mmdet3d.datasets.ray', 'mmdet3d/datasets/ray.py')
+    ds = load_ref('mmdet3d.datasets.nuscenes_dataset_occ', 'mmdet3d/datasets/nuscenes_dataset_occ.py')
+
+    seed, T, N, P, H, W, focal = 41, 2, 2, 3001, 48, 80, 40.0
+    S_ = RN.synthetic_sample(seed, T=T, N=N, P=P, H=H, W=W, focal=focal)
+    depth_lists, seg_lists = RN.stage_a(S_['points'], S_['labels'], RN.LUT, S_['poses'], N, H, W)
+    with tempfile.TemporaryDirectory() as tmp:
+        os.makedirs(os.path.join(tmp, 'depth'))
+        os.makedirs(os.path.join(tmp, 'seg'))
+        for t, info in enumerate(S_['infos']):
+            for c, name in enumerate(S_['cam_names']):
+                v = t * N + c
+                path = os.path.join(tmp, 'frame_%d.png' % v)
+                Image.fromarray(S_['frames'][v], 'RGB').save(path)
+                info['cams'][name]['data_path'] = path
+                depth_lists[v].flatten().tofile(os.path.join(tmp, 'depth', 'frame_%d.png.bin' % v))
+                seg_lists[v].flatten().tofile(os.path.join(tmp, 'seg', 'frame_%d.png.bin' % v))
+        real_load_seg = ds.load_seg_label
+        ds.load_seg_label = lambda path, gt, img_size=[H, W], mode='lidarseg': real_load_seg(path, gt, img_size=img_size, mode=mode)
+        # the reference's load_img asks numpy for a conversion without a copy, which NumPy 2 refuses (1.x, which the reference
+        # stack runs, copies silently); stood in for by the same behaviour: the decoded RGB frame as float32, divided by 255 in
+        # float32
+        ds.load_img = lambda path: np.asarray(Image.open(path).convert('RGB'), dtype=np.float32) / 255.0
+        recorded = {}
+        real_generate = ds.generate_rays
+
+        def recording_generate(*a, **k):
+            recorded['args'], recorded['kw'] = a, k
+            return real_generate(*a, **k)
+        ds.generate_rays = recording_generate
+
+        class Self:
+            data_infos = S_['infos']
+            aux_frames = [1]
+            semantic_gt_path = os.path.join(tmp, 'seg')
+            depth_gt_path = os.path.join(tmp, 'depth')
+            max_ray_nums = 0
+            WRS_balance_weight = None
+            dynamic_class = torch.tensor(ds.dynamic_class)
+            normalize_rgb = staticmethod(lambda img: (torch.from_numpy(img).permute(2, 0, 1).contiguous() - mean[:, None, None]) / std[:, None, None])
+        table = ds.NuScenesDatasetOccpancy.get_rays(Self(), 0)
+    coors, depths, segs, imgs, c2w, Ks = recorded['args'][:6]
+    time_ids, dyn = recorded['kw']['time_ids'], recorded['kw']['dynamic_class']
+    captured = {}
+
+    class Capture:
+        def __init__(self, weights, num_samples, replacement):
+            captured['w'] = weights.clone()
+            self.n = num_samples
+
+        def __iter__(self):
+            return iter(range(self.n))
+    ray.WeightedRandomSampler = Capture
+    ray.generate_rays(coors, depths, segs, imgs, c2w, Ks, max_ray_nums=100, time_ids=time_ids, dynamic_class=dyn,
+                      balance_weight=None, weight_adj=0.3, weight_dyn=0.0, use_wrs=True)
+    w_batch = captured['w'].numpy()
+    bw = torch.exp(0.005 * (torch.arange(1, 18).float().max() / torch.arange(1, 18).float() - 1))
+    ray.generate_rays(coors, depths, segs, imgs, c2w, Ks, max_ray_nums=100, time_ids=time_ids, dynamic_class=dyn,
+                      balance_weight=bw, weight_adj=0.25, weight_dyn=0.1, use_wrs=True)
+    assert {int(k): list(v) for k, v in time_ids.items()} == {0: [0, 1], 1: [2, 3]}
+    save('ray_labels_small.npz', seed=np.int64(seed), shape=np.array([T, N, P, H, W], np.int64), focal=np.float64(focal),
+         depth_list=np.concatenate(depth_lists), seg_list=np.concatenate(seg_lists), view_off=RN.offsets(depth_lists),
+         frames=S_['frames'], c2w=c2w.numpy(), K=torch.stack(Ks).numpy(), dynamic_class=dyn.numpy().astype(np.int32),
+         table=table.numpy(), weights_batch=w_batch, balance_weight=bw.numpy(), weights_given=captured['w'].numpy(),
+         weight_adj_dyn=np.array([0.25, 0.1]))
+
+
 def gen_stereo(vtm):
     """G12: DepthNet.gen_grid + calculate_cost_volumn (view_transformer.py:546-604)
     called as plain functions (the DepthNet constructor needs mmcv; the two methods only read self.bias)."""
@@ -1526,6 +1621,8 @@ def main():
         gen_e2e_train_b2(vtm, occ)
     if want('fscore'):
         gen_fscore(om)
+    if want('ray_labels'):
+        gen_ray_labels()
     if only:
         return
     gen_kat(bp)
