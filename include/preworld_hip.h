@@ -795,6 +795,9 @@ int pw_copy_many(const void* const* src, void* const* dst, const size_t* bytes, 
  * declared in preworld_hip_rays.h, a part of this ABI kept in a file of its own for the same reason. */
 #include "preworld_hip_rays.h"
 
+/* The image side's Swin shifted-window attention (pw_swin_window_attention) is declared in preworld_hip_swin.h, likewise. */
+#include "preworld_hip_swin.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,8 @@ HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip.h')
 OPTIM_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip_optim.h')      # the part preworld_hip.h includes (pw_optim_*)
 RAYS_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip_rays.h')        # ... and the ray-supervision part (pw_ray_*)
 
+SWIN_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip_swin.h')        # ... and the Swin window attention (pw_swin_*)
+
 _CTYPES = {
     'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64,
     'size_t': ctypes.c_size_t, 'float': ctypes.c_float, 'double': ctypes.c_double,
@@ -152,6 +154,8 @@ _optim_protos, PW_OPTIM = _parse(OPTIM_HEADER_PATH)        # ... and those of th
 _protos.update(_optim_protos)
 _rays_protos, PW_RAYS = _parse(RAYS_HEADER_PATH)           # ... and those of the ray-supervision part (PW_RAY_*)
 _protos.update(_rays_protos)
+_swin_protos, PW_SWIN = _parse(SWIN_HEADER_PATH)           # ... and those of the Swin window attention (PW_SWIN_*)
+_protos.update(_swin_protos)
 _lib = None
 _fns = {}
 

@@ -15,6 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(CSRC, 'libpreworld_hip.so')
 ARCH = 'gfx950'
+ABI_HEADERS = ('preworld_hip.h', 'preworld_hip_optim.h', 'preworld_hip_rays.h', 'preworld_hip_swin.h')      # include/: hashed, and every object depends on them
 
 COMMON = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-fvisibility=hidden',
           '-Wall', '-Wno-unused-function', '-fno-gpu-rdc']
@@ -49,7 +50,7 @@ def source_hash():
     import hashlib
     h = hashlib.sha256()
     files = sorted(f for f in os.listdir(CSRC) if f.endswith(('.hip', '.h')))
-    for f in files + [os.path.join('..', '..', 'include', h) for h in ('preworld_hip.h', 'preworld_hip_optim.h', 'preworld_hip_rays.h')]:
+    for f in files + [os.path.join('..', '..', 'include', h) for h in ABI_HEADERS]:
         h.update(os.path.basename(f).encode() + b'\0')
         h.update(open(os.path.join(CSRC, f), 'rb').read())
     return h.hexdigest()[:16]
@@ -76,7 +77,7 @@ def _compile(src, force, verbose):
                                         if h.endswith('.h')]
     if src == 'pw_core.hip':
         deps.append(os.path.join(CSRC, 'pw_build_id.inc'))
-    deps += [os.path.join(HERE, '..', 'include', h) for h in ('preworld_hip.h', 'preworld_hip_optim.h', 'preworld_hip_rays.h')]
+    deps += [os.path.join(HERE, '..', 'include', h) for h in ABI_HEADERS]
     if not force and not _needs_build(obj, deps):
         return obj, False
     cmd = ['hipcc'] + COMMON + EXTRA.get(src, []) + ['-c', os.path.join(CSRC, src), '-o', obj]

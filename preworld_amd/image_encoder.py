@@ -1,7 +1,9 @@
 """the image side of the detector in plain torch.nn (no mmcv / mmdet / mmseg), so that a true
-image -> occupancy samples/s can be reported.  Nothing here is a custom kernel: the reference keeps these modules on
-PyTorch and so does this package (north_star: "the multi-camera backbone stays on PyTorch-ROCm"); only the DepthNet's
-stereo cost volume and its softmax tail call the HIP library (ops.stereo_cost_volume, ops.depthnet_tail -- rows 8f.1).
+image -> occupancy samples/s can be reported.  The reference keeps these modules on PyTorch and by default so does this
+package (north_star: "the multi-camera backbone stays on PyTorch-ROCm").  Three things call the HIP library: the DepthNet's
+stereo cost volume and its softmax tail (ops.stereo_cost_volume, ops.depthnet_tail -- rows 8f.1) and, only when asked for with
+attn_impl='hip', the Swin blocks' shifted-window attention (ops.swin_window_attention, one launch per block between the qkv
+and proj Linears -- DESIGN.md 17; forward only, the default 'torch' path is unchanged).
 
 State-dict keys, constructor arguments and forward contracts are the reference's, so released checkpoints load:
 
@@ -63,9 +65,28 @@ class PatchMerging(nn.Module):
         return self.reduction(x), ((H + 1) // 2, (W + 1) // 2)
 
 
+ATTN_IMPLS = ('torch', 'hip')
+
+
+def _check_attn_impl(attn_impl, embed_dims, num_heads, ws):
+    """'hip' has no fallback: a config pw_swin_window_attention does not take is refused where the module is built"""
+    if attn_impl not in ATTN_IMPLS:
+        raise ValueError('attn_impl must be one of %s, got %r' % (ATTN_IMPLS, attn_impl))
+    if attn_impl == 'hip':
+        from . import ops
+        why = ops.swin_attention_supported(embed_dims, num_heads, ws)
+        if why is not None:
+            raise ValueError("attn_impl='hip': the fused window attention does not support this block: " + why)
+    return attn_impl
+
+
 class WindowMSA(nn.Module):
-    def __init__(self, embed_dims, num_heads, window_size, qkv_bias=True, qk_scale=None):
+    """attn_impl is recorded here for ShiftWindowMSA, which owns the fused path (it needs the un-partitioned map); forward() is the
+    torch path whatever it says."""
+
+    def __init__(self, embed_dims, num_heads, window_size, qkv_bias=True, qk_scale=None, attn_impl='torch'):
         super().__init__()
+        self.attn_impl = _check_attn_impl(attn_impl, embed_dims, num_heads, max(window_size))
         self.embed_dims, self.window_size, self.num_heads = embed_dims, window_size, num_heads
         self.scale = qk_scale or (embed_dims // num_heads) ** -0.5
         Wh, Ww = window_size
@@ -96,11 +117,36 @@ class WindowMSA(nn.Module):
 
 
 class ShiftWindowMSA(nn.Module):
-    def __init__(self, embed_dims, num_heads, window_size, shift_size=0, qkv_bias=True, qk_scale=None):
+    """attn_impl='torch' (default): pad, roll, window partition, WindowMSA, reverse, roll back, crop, as the reference.
+    attn_impl='hip': qkv Linear on the (B, H*W, C) tokens, ops.swin_window_attention (one HIP launch that does pad, roll, partition,
+    bias, shift mask, softmax and their inverses as index arithmetic), proj Linear; no mask cache, no window-ordered tensor.  The
+    kernel is forward only: when autograd would need a backward (grad enabled and the input or a parameter of the attention requires
+    grad) 'hip' runs the torch path, so training is unchanged.  Parameters, buffers and state-dict keys are the same for both."""
+
+    def __init__(self, embed_dims, num_heads, window_size, shift_size=0, qkv_bias=True, qk_scale=None, attn_impl='torch'):
         super().__init__()
         self.window_size, self.shift_size = window_size, shift_size
-        self.w_msa = WindowMSA(embed_dims, num_heads, (window_size, window_size), qkv_bias, qk_scale)
+        self.w_msa = WindowMSA(embed_dims, num_heads, (window_size, window_size), qkv_bias, qk_scale, attn_impl)
+        self.attn_impl = self.w_msa.attn_impl
         self._mask_cache = {}
+
+    def set_attn_impl(self, attn_impl):
+        m = self.w_msa
+        self.attn_impl = m.attn_impl = _check_attn_impl(attn_impl, m.embed_dims, m.num_heads, self.window_size)
+
+    def _needs_backward(self, query):
+        return torch.is_grad_enabled() and (query.requires_grad or any(p.requires_grad for p in self.w_msa.parameters()))
+
+    def _forward_hip(self, query, hw_shape):
+        from . import ops
+        m = self.w_msa
+        qkv = m.qkv(query)                                                        # (B, H*W, 3C): Linears act per token
+        if not qkv.is_contiguous():
+            qkv = qkv.contiguous()
+        pad = None if m.qkv.bias is None else m.qkv.bias.detach().to(qkv.dtype)   # qkv of a zero (padded) token
+        x = ops.swin_window_attention(qkv, pad, m.relative_position_bias_table.detach().float(), hw_shape[0], hw_shape[1],
+                                      m.num_heads, self.window_size, self.shift_size, m.scale)
+        return m.proj(x)
 
     def _partition(self, x):
         B, H, W, C = x.shape
@@ -134,6 +180,8 @@ class ShiftWindowMSA(nn.Module):
         return m
 
     def forward(self, query, hw_shape):
+        if self.attn_impl == 'hip' and not self._needs_backward(query):
+            return self._forward_hip(query, hw_shape)
         B, L, C = query.shape
         H, W = hw_shape
         ws, ss = self.window_size, self.shift_size
@@ -168,10 +216,12 @@ class FFN(nn.Module):
 
 
 class SwinBlock(nn.Module):
-    def __init__(self, embed_dims, num_heads, feedforward_channels, window_size, shift, qkv_bias=True, qk_scale=None):
+    def __init__(self, embed_dims, num_heads, feedforward_channels, window_size, shift, qkv_bias=True, qk_scale=None,
+                 attn_impl='torch'):
         super().__init__()
         self.norm1 = nn.LayerNorm(embed_dims)
-        self.attn = ShiftWindowMSA(embed_dims, num_heads, window_size, window_size // 2 if shift else 0, qkv_bias, qk_scale)
+        self.attn = ShiftWindowMSA(embed_dims, num_heads, window_size, window_size // 2 if shift else 0, qkv_bias, qk_scale,
+                                   attn_impl)
         self.norm2 = nn.LayerNorm(embed_dims)
         self.ffn = FFN(embed_dims, feedforward_channels)
 
@@ -182,10 +232,10 @@ class SwinBlock(nn.Module):
 
 class SwinBlockSequence(nn.Module):
     def __init__(self, embed_dims, num_heads, feedforward_channels, depth, window_size, downsample, qkv_bias=True,
-                 qk_scale=None):
+                 qk_scale=None, attn_impl='torch'):
         super().__init__()
         self.blocks = nn.ModuleList([SwinBlock(embed_dims, num_heads, feedforward_channels, window_size, i % 2 == 1,
-                                               qkv_bias, qk_scale) for i in range(depth)])
+                                               qkv_bias, qk_scale, attn_impl) for i in range(depth)])
         self.downsample = downsample
 
     def forward(self, x, hw_shape):
@@ -199,7 +249,8 @@ class SwinBlockSequence(nn.Module):
 
 class SwinTransformer(nn.Module):
     """Same constructor arguments as the reference (those that only matter for training / checkpoint loading are
-    accepted and ignored).  forward(x (BN,3,H,W)) -> list: [stage-0 feature un-normed if return_stereo_feat] +
+    accepted and ignored), plus attn_impl: 'torch' (default) or 'hip', the fused window attention of ShiftWindowMSA, which a config
+    selects with dict(type='SwinTransformer', ..., attn_impl='hip').  forward(x (BN,3,H,W)) -> list: [stage-0 feature un-normed if return_stereo_feat] +
     [norm_i(stage i) for i in out_indices], each (BN, C_i, H_i, W_i) -- swin.py:946-971."""
 
     def __init__(self, pretrain_img_size=224, in_channels=3, embed_dims=96, patch_size=4, window_size=7, mlp_ratio=4,
@@ -207,7 +258,7 @@ class SwinTransformer(nn.Module):
                  qkv_bias=True, qk_scale=None, patch_norm=True, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.1,
                  use_abs_pos_embed=False, act_cfg=None, norm_cfg=None, pretrain_style='official', pretrained=None,
                  init_cfg=None, with_cp=True, return_stereo_feat=False, output_missing_index_as_none=False,
-                 frozen_stages=-1):
+                 frozen_stages=-1, attn_impl='torch'):
         super().__init__()
         assert strides[0] == patch_size, 'Use non-overlapping patch embed.'
         if use_abs_pos_embed:
@@ -215,6 +266,7 @@ class SwinTransformer(nn.Module):
         self.out_indices, self.return_stereo_feat = tuple(out_indices), return_stereo_feat
         self.output_missing_index_as_none = output_missing_index_as_none
         self.use_abs_pos_embed = False
+        self.attn_impl = attn_impl
         self.patch_embed = PatchEmbed(in_channels, embed_dims, patch_size, strides[0], norm=patch_norm)
         self.drop_after_pos = nn.Dropout(p=drop_rate)
         self.stages = nn.ModuleList()
@@ -222,12 +274,22 @@ class SwinTransformer(nn.Module):
         for i in range(len(depths)):
             down = PatchMerging(c, 2 * c, strides[i + 1], norm=patch_norm) if i < len(depths) - 1 else None
             self.stages.append(SwinBlockSequence(c, num_heads[i], mlp_ratio * c, depths[i], window_size, down, qkv_bias,
-                                                 qk_scale))
+                                                 qk_scale, attn_impl))
             if down is not None:
                 c = down.out_channels
         self.num_features = [int(embed_dims * 2 ** i) for i in range(len(depths))]
         for i in self.out_indices:
             self.add_module('norm%d' % i, nn.LayerNorm(self.num_features[i]))
+
+    def set_attn_impl(self, attn_impl):
+        """switch every block of a built model between 'torch' and 'hip' (the fused window attention); an unsupported block raises
+        before any block is switched"""
+        blocks = [m for m in self.modules() if isinstance(m, ShiftWindowMSA)]
+        for m in blocks:
+            _check_attn_impl(attn_impl, m.w_msa.embed_dims, m.w_msa.num_heads, m.window_size)
+        for m in blocks:
+            m.set_attn_impl(attn_impl)
+        self.attn_impl = attn_impl
 
     def _to_map(self, out, hw, i, channels_last=False):
         m = out.view(-1, *hw, self.num_features[i]).permute(0, 3, 1, 2)

@@ -2059,3 +2059,50 @@ def optim_update(plan, n_rows, n_chunks, hyper, n_groups, slab, ctr, ema_updates
     _lib.call('pw_optim_update', plan, plan.numel() * 8, n_rows, n_chunks, hyper, n_groups, slab, int(use_norm), int(clip),
               int(use_ema), int(skip_nonfinite), ctr, ema_updates, norm_out, _lib.STREAM)
     OPTIM_LAUNCHES['update'] += 1
+
+
+# ------------------------------------------------------------------------------ Swin window attention (preworld_amd/image_encoder.py)
+SWIN_MAX_WS, SWIN_MAX_HEAD_DIM = _lib.PW_SWIN['PW_SWIN_MAX_WS'], _lib.PW_SWIN['PW_SWIN_MAX_HEAD_DIM']
+
+
+def swin_attention_supported(embed_dims, num_heads, ws):
+    """None if pw_swin_window_attention takes this (embed_dims, num_heads, window), else the reason it does not"""
+    if embed_dims % num_heads:
+        return 'embed_dims %d is no multiple of num_heads %d' % (embed_dims, num_heads)
+    d = embed_dims // num_heads
+    if not 2 <= ws <= SWIN_MAX_WS:
+        return 'window %d outside 2 .. %d' % (ws, SWIN_MAX_WS)
+    if d > SWIN_MAX_HEAD_DIM or d % 4:
+        return 'head width %d (supported: multiples of 4 up to %d)' % (d, SWIN_MAX_HEAD_DIM)
+    return None
+
+
+def swin_window_attention(qkv, pad_qkv, bias_table, H, W, num_heads, ws, shift, scale):
+    """Shifted-window attention of one Swin block in one launch (include/preworld_hip_swin.h): qkv (B, H*W, 3C) or (B, H, W, 3C), the
+    qkv Linear applied to the un-padded, un-rolled tokens, fp32 or bf16; pad_qkv (3C) in the same dtype = the Linear's output for a
+    zero token (its bias) or None for zeros; bias_table ((2 ws - 1)^2, num_heads) fp32.  Returns softmax(q k^T scale + bias + mask) v
+    as (B, H*W, C) / (B, H, W, C), the proj Linear's input.  Forward only; no workspace, no synchronisation."""
+    if qkv.dim() not in (3, 4) or (qkv.dim() == 3 and qkv.shape[1] != H * W) or (qkv.dim() == 4 and tuple(qkv.shape[1:3]) != (H, W)):
+        raise _lib.PreworldHipError('swin_window_attention: qkv must be (B, H*W, 3C) or (B, H, W, 3C) with H, W = %d, %d, got %s' % (H, W, tuple(qkv.shape)))
+    if qkv.dtype not in (_f32, torch.bfloat16):
+        raise _lib.PreworldHipError('swin_window_attention: qkv must be float32 or bfloat16, got %s' % qkv.dtype)
+    if not qkv.is_contiguous():
+        raise _lib.PreworldHipError('swin_window_attention: qkv must be contiguous')
+    B, C3 = qkv.shape[0], qkv.shape[-1]
+    if B < 1 or H < 1 or W < 1 or C3 % 3:
+        raise _lib.PreworldHipError('swin_window_attention: empty input or a last dimension that is no multiple of 3: %s' % (tuple(qkv.shape),))
+    C = C3 // 3
+    why = swin_attention_supported(C, num_heads, ws)
+    if why is not None:
+        raise _lib.PreworldHipError('swin_window_attention: not supported: ' + why)
+    if not 0 <= shift < ws:
+        raise _lib.PreworldHipError('swin_window_attention: need 0 <= shift < ws, got %d, %d' % (shift, ws))
+    if pad_qkv is not None and (tuple(pad_qkv.shape) != (C3,) or pad_qkv.dtype != qkv.dtype or not pad_qkv.is_contiguous()):
+        raise _lib.PreworldHipError('swin_window_attention: pad_qkv must be a contiguous (%d,) tensor of %s' % (C3, qkv.dtype))
+    if tuple(bias_table.shape) != ((2 * ws - 1) ** 2, num_heads) or bias_table.dtype != _f32 or not bias_table.is_contiguous():
+        raise _lib.PreworldHipError('swin_window_attention: bias_table must be a contiguous float32 (%d, %d) tensor, got %s %s'
+                                    % ((2 * ws - 1) ** 2, num_heads, bias_table.dtype, tuple(bias_table.shape)))
+    out = torch.empty(qkv.shape[:-1] + (C,), device=qkv.device, dtype=qkv.dtype)
+    _lib.call('pw_swin_window_attention', qkv, pad_qkv, bias_table, out, B, H, W, C, num_heads, ws, shift, float(scale),
+              _lib.PW_SWIN['PW_SWIN_BF16' if qkv.dtype == torch.bfloat16 else 'PW_SWIN_F32'], _lib.STREAM)
+    return out
