@@ -798,6 +798,9 @@ int pw_copy_many(const void* const* src, void* const* dst, const size_t* bytes, 
 /* The image side's Swin shifted-window attention (pw_swin_window_attention) is declared in preworld_hip_swin.h, likewise. */
 #include "preworld_hip_swin.h"
 
+/* ... and its gradient (pw_swin_window_attention_backward) in preworld_hip_swin_bwd.h. */
+#include "preworld_hip_swin_bwd.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,7 @@ OPTIM_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip_optim.h')
 RAYS_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip_rays.h')        # ... and the ray-supervision part (pw_ray_*)
 
 SWIN_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip_swin.h')        # ... and the Swin window attention (pw_swin_*)
+SWIN_BWD_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip_swin_bwd.h')      # ... and its gradient
 
 _CTYPES = {
     'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64,
@@ -156,6 +157,8 @@ _rays_protos, PW_RAYS = _parse(RAYS_HEADER_PATH)           # ... and those of th
 _protos.update(_rays_protos)
 _swin_protos, PW_SWIN = _parse(SWIN_HEADER_PATH)           # ... and those of the Swin window attention (PW_SWIN_*)
 _protos.update(_swin_protos)
+_swin_bwd_protos, PW_SWIN_BWD = _parse(SWIN_BWD_HEADER_PATH)      # ... and those of its gradient (PW_SWIN_BWD_*)
+_protos.update(_swin_bwd_protos)
 _lib = None
 _fns = {}
 

@@ -3,7 +3,8 @@ image -> occupancy samples/s can be reported.  The reference keeps these modules
 package (north_star: "the multi-camera backbone stays on PyTorch-ROCm").  Three things call the HIP library: the DepthNet's
 stereo cost volume and its softmax tail (ops.stereo_cost_volume, ops.depthnet_tail -- rows 8f.1) and, only when asked for with
 attn_impl='hip', the Swin blocks' shifted-window attention (ops.swin_window_attention, one launch per block between the qkv
-and proj Linears -- DESIGN.md 17; forward only, the default 'torch' path is unchanged).
+and proj Linears -- DESIGN.md 17; forward only, the default 'torch' path is unchanged; attn_impl='hip_grad' adds the kernel's
+HIP backward, ops.swin_window_attention_backward -- DESIGN.md 17b).
 
 State-dict keys, constructor arguments and forward contracts are the reference's, so released checkpoints load:
 
@@ -65,18 +66,18 @@ class PatchMerging(nn.Module):
         return self.reduction(x), ((H + 1) // 2, (W + 1) // 2)
 
 
-ATTN_IMPLS = ('torch', 'hip')
+ATTN_IMPLS = ('torch', 'hip', 'hip_grad')
 
 
 def _check_attn_impl(attn_impl, embed_dims, num_heads, ws):
-    """'hip' has no fallback: a config pw_swin_window_attention does not take is refused where the module is built"""
+    """'hip' and 'hip_grad' have no fallback: a config pw_swin_window_attention does not take is refused where the module is built"""
     if attn_impl not in ATTN_IMPLS:
         raise ValueError('attn_impl must be one of %s, got %r' % (ATTN_IMPLS, attn_impl))
-    if attn_impl == 'hip':
+    if attn_impl != 'torch':
         from . import ops
         why = ops.swin_attention_supported(embed_dims, num_heads, ws)
         if why is not None:
-            raise ValueError("attn_impl='hip': the fused window attention does not support this block: " + why)
+            raise ValueError("attn_impl=%r: the fused window attention does not support this block: %s" % (attn_impl, why))
     return attn_impl
 
 
@@ -121,7 +122,11 @@ class ShiftWindowMSA(nn.Module):
     attn_impl='hip': qkv Linear on the (B, H*W, C) tokens, ops.swin_window_attention (one HIP launch that does pad, roll, partition,
     bias, shift mask, softmax and their inverses as index arithmetic), proj Linear; no mask cache, no window-ordered tensor.  The
     kernel is forward only: when autograd would need a backward (grad enabled and the input or a parameter of the attention requires
-    grad) 'hip' runs the torch path, so training is unchanged.  Parameters, buffers and state-dict keys are the same for both."""
+    grad) 'hip' runs the torch path, so training is unchanged; 'hip_grad' is the mode that trains through the kernel.
+    attn_impl='hip_grad': without grad exactly 'hip'; with grad qkv Linear, ops.SwinWindowAttention (the same forward launch, its
+    gradient is ops.swin_window_attention_backward: dqkv, and through the un-detached table and qkv.bias the gradients of both
+    parameters), proj Linear.  The torch path never runs and no mask is cached; a host tensor is refused, never a fallback.
+    Parameters, buffers and state-dict keys are the same for all three."""
 
     def __init__(self, embed_dims, num_heads, window_size, shift_size=0, qkv_bias=True, qk_scale=None, attn_impl='torch'):
         super().__init__()
@@ -146,6 +151,17 @@ class ShiftWindowMSA(nn.Module):
         pad = None if m.qkv.bias is None else m.qkv.bias.detach().to(qkv.dtype)   # qkv of a zero (padded) token
         x = ops.swin_window_attention(qkv, pad, m.relative_position_bias_table.detach().float(), hw_shape[0], hw_shape[1],
                                       m.num_heads, self.window_size, self.shift_size, m.scale)
+        return m.proj(x)
+
+    def _forward_hip_grad(self, query, hw_shape):
+        from . import ops
+        m = self.w_msa
+        qkv = m.qkv(query)
+        if not qkv.is_contiguous():
+            qkv = qkv.contiguous()
+        pad = None if m.qkv.bias is None else m.qkv.bias.to(qkv.dtype)            # not detached: it receives dpad_qkv
+        x = ops.SwinWindowAttention.apply(qkv, pad, m.relative_position_bias_table.float(), hw_shape[0], hw_shape[1],
+                                          m.num_heads, self.window_size, self.shift_size, m.scale)
         return m.proj(x)
 
     def _partition(self, x):
@@ -180,8 +196,11 @@ class ShiftWindowMSA(nn.Module):
         return m
 
     def forward(self, query, hw_shape):
-        if self.attn_impl == 'hip' and not self._needs_backward(query):
-            return self._forward_hip(query, hw_shape)
+        if self.attn_impl != 'torch':
+            if not self._needs_backward(query):
+                return self._forward_hip(query, hw_shape)
+            if self.attn_impl == 'hip_grad':
+                return self._forward_hip_grad(query, hw_shape)
         B, L, C = query.shape
         H, W = hw_shape
         ws, ss = self.window_size, self.shift_size
@@ -249,8 +268,8 @@ class SwinBlockSequence(nn.Module):
 
 class SwinTransformer(nn.Module):
     """Same constructor arguments as the reference (those that only matter for training / checkpoint loading are
-    accepted and ignored), plus attn_impl: 'torch' (default) or 'hip', the fused window attention of ShiftWindowMSA, which a config
-    selects with dict(type='SwinTransformer', ..., attn_impl='hip').  forward(x (BN,3,H,W)) -> list: [stage-0 feature un-normed if return_stereo_feat] +
+    accepted and ignored), plus attn_impl: 'torch' (default), 'hip', the fused window attention of ShiftWindowMSA (forward only), or
+    'hip_grad', the same with its HIP backward; a config selects one with dict(type='SwinTransformer', ..., attn_impl='hip').  forward(x (BN,3,H,W)) -> list: [stage-0 feature un-normed if return_stereo_feat] +
     [norm_i(stage i) for i in out_indices], each (BN, C_i, H_i, W_i) -- swin.py:946-971."""
 
     def __init__(self, pretrain_img_size=224, in_channels=3, embed_dims=96, patch_size=4, window_size=7, mlp_ratio=4,
@@ -282,7 +301,7 @@ class SwinTransformer(nn.Module):
             self.add_module('norm%d' % i, nn.LayerNorm(self.num_features[i]))
 
     def set_attn_impl(self, attn_impl):
-        """switch every block of a built model between 'torch' and 'hip' (the fused window attention); an unsupported block raises
+        """switch every block of a built model between 'torch', 'hip' and 'hip_grad' (the fused window attention); an unsupported block raises
         before any block is switched"""
         blocks = [m for m in self.modules() if isinstance(m, ShiftWindowMSA)]
         for m in blocks:

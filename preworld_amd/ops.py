@@ -2077,32 +2077,88 @@ def swin_attention_supported(embed_dims, num_heads, ws):
     return None
 
 
+def _swin_check(fn, qkv, pad_qkv, bias_table, H, W, num_heads, ws, shift):
+    """the argument checks the forward and the backward wrapper share; returns (B, C)"""
+    if qkv.dim() not in (3, 4) or (qkv.dim() == 3 and qkv.shape[1] != H * W) or (qkv.dim() == 4 and tuple(qkv.shape[1:3]) != (H, W)):
+        raise _lib.PreworldHipError('%s: qkv must be (B, H*W, 3C) or (B, H, W, 3C) with H, W = %d, %d, got %s' % (fn, H, W, tuple(qkv.shape)))
+    if qkv.dtype not in (_f32, torch.bfloat16):
+        raise _lib.PreworldHipError('%s: qkv must be float32 or bfloat16, got %s' % (fn, qkv.dtype))
+    if not qkv.is_contiguous():
+        raise _lib.PreworldHipError('%s: qkv must be contiguous' % fn)
+    B, C3 = qkv.shape[0], qkv.shape[-1]
+    if B < 1 or H < 1 or W < 1 or C3 % 3:
+        raise _lib.PreworldHipError('%s: empty input or a last dimension that is no multiple of 3: %s' % (fn, tuple(qkv.shape)))
+    C = C3 // 3
+    why = swin_attention_supported(C, num_heads, ws)
+    if why is not None:
+        raise _lib.PreworldHipError('%s: not supported: %s' % (fn, why))
+    if not 0 <= shift < ws:
+        raise _lib.PreworldHipError('%s: need 0 <= shift < ws, got %d, %d' % (fn, shift, ws))
+    if pad_qkv is not None and (tuple(pad_qkv.shape) != (C3,) or pad_qkv.dtype != qkv.dtype or not pad_qkv.is_contiguous()):
+        raise _lib.PreworldHipError('%s: pad_qkv must be a contiguous (%d,) tensor of %s' % (fn, C3, qkv.dtype))
+    if tuple(bias_table.shape) != ((2 * ws - 1) ** 2, num_heads) or bias_table.dtype != _f32 or not bias_table.is_contiguous():
+        raise _lib.PreworldHipError('%s: bias_table must be a contiguous float32 (%d, %d) tensor, got %s %s'
+                                    % (fn, (2 * ws - 1) ** 2, num_heads, bias_table.dtype, tuple(bias_table.shape)))
+    return B, C
+
+
 def swin_window_attention(qkv, pad_qkv, bias_table, H, W, num_heads, ws, shift, scale):
     """Shifted-window attention of one Swin block in one launch (include/preworld_hip_swin.h): qkv (B, H*W, 3C) or (B, H, W, 3C), the
     qkv Linear applied to the un-padded, un-rolled tokens, fp32 or bf16; pad_qkv (3C) in the same dtype = the Linear's output for a
     zero token (its bias) or None for zeros; bias_table ((2 ws - 1)^2, num_heads) fp32.  Returns softmax(q k^T scale + bias + mask) v
     as (B, H*W, C) / (B, H, W, C), the proj Linear's input.  Forward only; no workspace, no synchronisation."""
-    if qkv.dim() not in (3, 4) or (qkv.dim() == 3 and qkv.shape[1] != H * W) or (qkv.dim() == 4 and tuple(qkv.shape[1:3]) != (H, W)):
-        raise _lib.PreworldHipError('swin_window_attention: qkv must be (B, H*W, 3C) or (B, H, W, 3C) with H, W = %d, %d, got %s' % (H, W, tuple(qkv.shape)))
-    if qkv.dtype not in (_f32, torch.bfloat16):
-        raise _lib.PreworldHipError('swin_window_attention: qkv must be float32 or bfloat16, got %s' % qkv.dtype)
-    if not qkv.is_contiguous():
-        raise _lib.PreworldHipError('swin_window_attention: qkv must be contiguous')
-    B, C3 = qkv.shape[0], qkv.shape[-1]
-    if B < 1 or H < 1 or W < 1 or C3 % 3:
-        raise _lib.PreworldHipError('swin_window_attention: empty input or a last dimension that is no multiple of 3: %s' % (tuple(qkv.shape),))
-    C = C3 // 3
-    why = swin_attention_supported(C, num_heads, ws)
-    if why is not None:
-        raise _lib.PreworldHipError('swin_window_attention: not supported: ' + why)
-    if not 0 <= shift < ws:
-        raise _lib.PreworldHipError('swin_window_attention: need 0 <= shift < ws, got %d, %d' % (shift, ws))
-    if pad_qkv is not None and (tuple(pad_qkv.shape) != (C3,) or pad_qkv.dtype != qkv.dtype or not pad_qkv.is_contiguous()):
-        raise _lib.PreworldHipError('swin_window_attention: pad_qkv must be a contiguous (%d,) tensor of %s' % (C3, qkv.dtype))
-    if tuple(bias_table.shape) != ((2 * ws - 1) ** 2, num_heads) or bias_table.dtype != _f32 or not bias_table.is_contiguous():
-        raise _lib.PreworldHipError('swin_window_attention: bias_table must be a contiguous float32 (%d, %d) tensor, got %s %s'
-                                    % ((2 * ws - 1) ** 2, num_heads, bias_table.dtype, tuple(bias_table.shape)))
+    B, C = _swin_check('swin_window_attention', qkv, pad_qkv, bias_table, H, W, num_heads, ws, shift)
     out = torch.empty(qkv.shape[:-1] + (C,), device=qkv.device, dtype=qkv.dtype)
     _lib.call('pw_swin_window_attention', qkv, pad_qkv, bias_table, out, B, H, W, C, num_heads, ws, shift, float(scale),
               _lib.PW_SWIN['PW_SWIN_BF16' if qkv.dtype == torch.bfloat16 else 'PW_SWIN_F32'], _lib.STREAM)
     return out
+
+
+def swin_backward_workspace_bytes(B, H, W, num_heads, ws):
+    """the workspace formula of include/preworld_hip_swin_bwd.h: one partial of (2 ws - 1)^2 + 64 floats per (window, head)"""
+    return 4 * B * (-(-H // ws)) * (-(-W // ws)) * num_heads * ((2 * ws - 1) ** 2 + _lib.PW_SWIN_BWD['PW_SWIN_BWD_PAD_SLOTS'])
+
+
+def swin_window_attention_backward(qkv, pad_qkv, bias_table, out, dout, H, W, num_heads, ws, shift, scale, need_pad=True, need_table=True):
+    """Gradient of swin_window_attention in two launches (include/preworld_hip_swin_bwd.h): qkv, pad_qkv, bias_table as the forward
+    took them, out what it returned, dout the gradient of out (same shape and dtype, contiguous).  Returns (dqkv like qkv,
+    dpad_qkv (3C) float32 or None, dbias_table like bias_table or None); dpad_qkv is None when pad_qkv is None or need_pad is False,
+    dbias_table when need_table is False.  Allocates the workspace of partials; deterministic, no synchronisation, no fallback."""
+    fn = 'swin_window_attention_backward'
+    B, C = _swin_check(fn, qkv, pad_qkv, bias_table, H, W, num_heads, ws, shift)
+    for name, t in (('out', out), ('dout', dout)):
+        if tuple(t.shape) != tuple(qkv.shape[:-1]) + (C,) or t.dtype != qkv.dtype or not t.is_contiguous():
+            raise _lib.PreworldHipError('%s: %s must be a contiguous %s tensor of shape %s, got %s %s'
+                                        % (fn, name, qkv.dtype, tuple(qkv.shape[:-1]) + (C,), t.dtype, tuple(t.shape)))
+    dev = qkv.device
+    dqkv = torch.empty_like(qkv)
+    dpad = torch.empty(3 * C, device=dev, dtype=_f32) if need_pad and pad_qkv is not None else None
+    dtable = torch.empty_like(bias_table) if need_table else None
+    nbytes = swin_backward_workspace_bytes(B, H, W, num_heads, ws) if dpad is not None or dtable is not None else 0
+    wsp = torch.empty(nbytes // 4, device=dev, dtype=_f32) if nbytes else None
+    _lib.call('pw_swin_window_attention_backward', qkv, pad_qkv, bias_table, out, dout, dqkv, dpad, dtable, wsp, nbytes, B, H, W, C,
+              num_heads, ws, shift, float(scale), _lib.PW_SWIN['PW_SWIN_BF16' if qkv.dtype == torch.bfloat16 else 'PW_SWIN_F32'],
+              _lib.STREAM)
+    return dqkv, dpad, dtable
+
+
+class SwinWindowAttention(torch.autograd.Function):
+    """swin_window_attention with swin_window_attention_backward as its gradient: apply(qkv, pad_qkv or None, bias_table, H, W,
+    num_heads, ws, shift, scale).  The forward is the same call, so the same bits; saved are qkv, pad_qkv, bias_table and out."""
+
+    @staticmethod
+    def forward(ctx, qkv, pad_qkv, bias_table, H, W, num_heads, ws, shift, scale):
+        out = swin_window_attention(qkv, pad_qkv, bias_table, H, W, num_heads, ws, shift, scale)
+        ctx.save_for_backward(qkv, pad_qkv, bias_table, out)
+        ctx.cfg = (H, W, num_heads, ws, shift, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, pad_qkv, bias_table, out = ctx.saved_tensors
+        if not dout.is_contiguous():
+            dout = dout.contiguous()
+        need = ctx.needs_input_grad
+        dqkv, dpad, dtable = swin_window_attention_backward(qkv, pad_qkv, bias_table, out, dout, *ctx.cfg, need_pad=need[1],
+                                                            need_table=need[2])
+        return (dqkv if need[0] else None, None if dpad is None else dpad.to(pad_qkv.dtype), dtable) + (None,) * 6
