@@ -801,6 +801,9 @@ int pw_copy_many(const void* const* src, void* const* dst, const size_t* bytes, 
 /* ... and its gradient (pw_swin_window_attention_backward) in preworld_hip_swin_bwd.h. */
 #include "preworld_hip_swin_bwd.h"
 
+/* The Swin blocks' Linears with LayerNorm, GELU and residual fused in (pw_swin_linear*) are declared in preworld_hip_swin_linear.h. */
+#include "preworld_hip_swin_linear.h"
+
 #ifdef __cplusplus
 }
 #endif

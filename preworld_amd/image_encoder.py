@@ -4,7 +4,9 @@ package (north_star: "the multi-camera backbone stays on PyTorch-ROCm").  Three 
 stereo cost volume and its softmax tail (ops.stereo_cost_volume, ops.depthnet_tail -- rows 8f.1) and, only when asked for with
 attn_impl='hip', the Swin blocks' shifted-window attention (ops.swin_window_attention, one launch per block between the qkv
 and proj Linears -- DESIGN.md 17; forward only, the default 'torch' path is unchanged; attn_impl='hip_grad' adds the kernel's
-HIP backward, ops.swin_window_attention_backward -- DESIGN.md 17b).
+HIP backward, ops.swin_window_attention_backward -- DESIGN.md 17b) and, with linear_impl='hip' on top of a fused attention, the
+blocks' four Linears with both LayerNorms, the GELU and both residual additions fused in (ops.swin_linear, five calls per block
+-- DESIGN.md 17c; forward only, the default 'torch' is unchanged).
 
 State-dict keys, constructor arguments and forward contracts are the reference's, so released checkpoints load:
 
@@ -79,6 +81,26 @@ def _check_attn_impl(attn_impl, embed_dims, num_heads, ws):
         if why is not None:
             raise ValueError("attn_impl=%r: the fused window attention does not support this block: %s" % (attn_impl, why))
     return attn_impl
+
+
+LINEAR_IMPLS = ('torch', 'hip')
+
+
+def _check_linear_impl(linear_impl, attn_impl, embed_dims, feedforward_channels):
+    """'hip' has no fallback: it needs the fused attention (the block hands the kernel its qkv directly) and Linears that
+    pw_swin_linear takes, and is refused otherwise where the module is built"""
+    if linear_impl not in LINEAR_IMPLS:
+        raise ValueError('linear_impl must be one of %s, got %r' % (LINEAR_IMPLS, linear_impl))
+    if linear_impl != 'torch':
+        if attn_impl not in ('hip', 'hip_grad'):
+            raise ValueError("linear_impl=%r needs attn_impl 'hip' or 'hip_grad', got %r" % (linear_impl, attn_impl))
+        from . import ops
+        for K, N in ((embed_dims, 3 * embed_dims), (embed_dims, embed_dims), (embed_dims, feedforward_channels),
+                     (feedforward_channels, embed_dims)):
+            why = ops.swin_linear_supported(K, N)
+            if why is not None:
+                raise ValueError("linear_impl=%r: the fused Linears do not support this block: %s" % (linear_impl, why))
+    return linear_impl
 
 
 class WindowMSA(nn.Module):
@@ -235,26 +257,91 @@ class FFN(nn.Module):
 
 
 class SwinBlock(nn.Module):
+    """linear_impl='torch' (default): norm1, attention, residual, norm2, FFN as the reference.
+    linear_impl='hip' (needs attn_impl 'hip' or 'hip_grad'): five calls and no token-sized temporary but qkv, the attention output
+    and the hidden tensor -- qkv = Linear(LN1(x)); ops.swin_window_attention on that qkv; x1 = x + proj(attn);
+    h = GELU(fc1(LN2(x1))); x2 = x1 + fc2(h) (ops.swin_linear, include/preworld_hip_swin_linear.h: the GEMM, and in front of it a
+    small launch for the (M, 2) row statistics where the mode has any).  Forward only: when autograd
+    would need a backward the block runs exactly what linear_impl='torch' runs.  An fp32 block runs the split-fp16 mode, under
+    torch.autocast(bfloat16) the bf16 mode; a block whose residual stream is not float32 (.bfloat16(), .half()) is refused.  The
+    packed operands live in a modules.Derived cache keyed on the Linears' and LayerNorms' parameters; parameters, buffers and
+    state-dict keys do not depend on linear_impl."""
+
     def __init__(self, embed_dims, num_heads, feedforward_channels, window_size, shift, qkv_bias=True, qk_scale=None,
-                 attn_impl='torch'):
+                 attn_impl='torch', linear_impl='torch'):
         super().__init__()
+        self.embed_dims, self.feedforward_channels = embed_dims, feedforward_channels
         self.norm1 = nn.LayerNorm(embed_dims)
         self.attn = ShiftWindowMSA(embed_dims, num_heads, window_size, window_size // 2 if shift else 0, qkv_bias, qk_scale,
                                    attn_impl)
         self.norm2 = nn.LayerNorm(embed_dims)
         self.ffn = FFN(embed_dims, feedforward_channels)
+        self.linear_impl = _check_linear_impl(linear_impl, attn_impl, embed_dims, feedforward_channels)
+        self._derived = None
+
+    def check_linear_impl(self, linear_impl):
+        return _check_linear_impl(linear_impl, self.attn.attn_impl, self.embed_dims, self.feedforward_channels)
+
+    def set_linear_impl(self, linear_impl):
+        self.linear_impl = self.check_linear_impl(linear_impl)
+
+    def _needs_backward(self, x):
+        return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+
+    def _packed(self, dtype):
+        """(qkv, proj, fc1, fc2) packed for the mode `dtype`, rebuilt when a Linear's or LayerNorm's parameter changes"""
+        from . import ops
+        from .modules import Derived
+        if self._derived is None:
+            self._derived = Derived()
+        m, fc1, fc2 = self.attn.w_msa, self.ffn.layers[0][0], self.ffn.layers[1]
+
+        def build():
+            return (ops.swin_linear_pack(m.qkv.weight, m.qkv.bias, self.norm1.weight, self.norm1.bias, dtype=dtype),
+                    ops.swin_linear_pack(m.proj.weight, m.proj.bias, dtype=dtype),
+                    ops.swin_linear_pack(fc1.weight, fc1.bias, self.norm2.weight, self.norm2.bias, dtype=dtype),
+                    ops.swin_linear_pack(fc2.weight, fc2.bias, dtype=dtype))
+        return self._derived.get('swin_linear_%s' % dtype, (self.norm1, m.qkv, m.proj, self.norm2, fc1, fc2), build)
+
+    def _forward_fused(self, x, hw_shape):
+        from . import _lib, ops
+        m = self.attn.w_msa
+        params = [p for mod in (self.norm1, m.qkv, m.proj, self.norm2, self.ffn) for p in mod.parameters()]
+        dtype = torch.float32
+        if torch.is_autocast_enabled('cuda'):
+            dtype = torch.get_autocast_dtype('cuda')
+            if dtype != torch.bfloat16:
+                raise _lib.PreworldHipError("SwinBlock(linear_impl='hip'): autocast to %s is not supported, only torch.bfloat16" % dtype)
+            if x.dtype == torch.bfloat16:          # under autocast PatchMerging's Linear hands the next stage a bf16 map: the first block
+                x = x.float()                      # lifts it (exact) and the stage's residual stream is float32 from there on
+        if x.dtype != torch.float32 or any(p.dtype != torch.float32 for p in params):
+            raise _lib.PreworldHipError("SwinBlock(linear_impl='hip'): the residual stream and the parameters must be float32 (got x %s); "
+                                        "for bf16 run the float32 module under torch.autocast('cuda', torch.bfloat16)" % x.dtype)
+        qkv_p, proj_p, fc1_p, fc2_p = self._packed(dtype)
+        if not x.is_contiguous():
+            x = x.contiguous()
+        qkv = ops.swin_linear(x, qkv_p, ln=True, eps=self.norm1.eps)
+        # what qkv gives for a zero (padded) token is the Linear's own bias: the LayerNorm's beta is applied in the prologue, not folded
+        pad = None if m.qkv.bias is None else m.qkv.bias.detach().to(qkv.dtype)
+        a = ops.swin_window_attention(qkv, pad, m.relative_position_bias_table.detach(), hw_shape[0], hw_shape[1], m.num_heads,
+                                      self.attn.window_size, self.attn.shift_size, m.scale)
+        x = ops.swin_linear(a, proj_p, residual=x)
+        h = ops.swin_linear(x, fc1_p, ln=True, eps=self.norm2.eps, act='gelu')
+        return ops.swin_linear(h, fc2_p, residual=x)
 
     def forward(self, x, hw_shape):
+        if self.linear_impl == 'hip' and not self._needs_backward(x):
+            return self._forward_fused(x, hw_shape)
         x = self.attn(self.norm1(x), hw_shape) + x
         return self.ffn(self.norm2(x), identity=x)
 
 
 class SwinBlockSequence(nn.Module):
     def __init__(self, embed_dims, num_heads, feedforward_channels, depth, window_size, downsample, qkv_bias=True,
-                 qk_scale=None, attn_impl='torch'):
+                 qk_scale=None, attn_impl='torch', linear_impl='torch'):
         super().__init__()
         self.blocks = nn.ModuleList([SwinBlock(embed_dims, num_heads, feedforward_channels, window_size, i % 2 == 1,
-                                               qkv_bias, qk_scale, attn_impl) for i in range(depth)])
+                                               qkv_bias, qk_scale, attn_impl, linear_impl) for i in range(depth)])
         self.downsample = downsample
 
     def forward(self, x, hw_shape):
@@ -269,7 +356,9 @@ class SwinBlockSequence(nn.Module):
 class SwinTransformer(nn.Module):
     """Same constructor arguments as the reference (those that only matter for training / checkpoint loading are
     accepted and ignored), plus attn_impl: 'torch' (default), 'hip', the fused window attention of ShiftWindowMSA (forward only), or
-    'hip_grad', the same with its HIP backward; a config selects one with dict(type='SwinTransformer', ..., attn_impl='hip').  forward(x (BN,3,H,W)) -> list: [stage-0 feature un-normed if return_stereo_feat] +
+    'hip_grad', the same with its HIP backward; a config selects one with dict(type='SwinTransformer', ..., attn_impl='hip'); and
+    linear_impl: 'torch' (default) or 'hip', the blocks' Linears with LayerNorm, GELU and residual fused in (SwinBlock; needs a fused
+    attn_impl).  forward(x (BN,3,H,W)) -> list: [stage-0 feature un-normed if return_stereo_feat] +
     [norm_i(stage i) for i in out_indices], each (BN, C_i, H_i, W_i) -- swin.py:946-971."""
 
     def __init__(self, pretrain_img_size=224, in_channels=3, embed_dims=96, patch_size=4, window_size=7, mlp_ratio=4,
@@ -277,7 +366,7 @@ class SwinTransformer(nn.Module):
                  qkv_bias=True, qk_scale=None, patch_norm=True, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.1,
                  use_abs_pos_embed=False, act_cfg=None, norm_cfg=None, pretrain_style='official', pretrained=None,
                  init_cfg=None, with_cp=True, return_stereo_feat=False, output_missing_index_as_none=False,
-                 frozen_stages=-1, attn_impl='torch'):
+                 frozen_stages=-1, attn_impl='torch', linear_impl='torch'):
         super().__init__()
         assert strides[0] == patch_size, 'Use non-overlapping patch embed.'
         if use_abs_pos_embed:
@@ -286,6 +375,7 @@ class SwinTransformer(nn.Module):
         self.output_missing_index_as_none = output_missing_index_as_none
         self.use_abs_pos_embed = False
         self.attn_impl = attn_impl
+        self.linear_impl = linear_impl
         self.patch_embed = PatchEmbed(in_channels, embed_dims, patch_size, strides[0], norm=patch_norm)
         self.drop_after_pos = nn.Dropout(p=drop_rate)
         self.stages = nn.ModuleList()
@@ -293,7 +383,7 @@ class SwinTransformer(nn.Module):
         for i in range(len(depths)):
             down = PatchMerging(c, 2 * c, strides[i + 1], norm=patch_norm) if i < len(depths) - 1 else None
             self.stages.append(SwinBlockSequence(c, num_heads[i], mlp_ratio * c, depths[i], window_size, down, qkv_bias,
-                                                 qk_scale, attn_impl))
+                                                 qk_scale, attn_impl, linear_impl))
             if down is not None:
                 c = down.out_channels
         self.num_features = [int(embed_dims * 2 ** i) for i in range(len(depths))]
@@ -309,6 +399,16 @@ class SwinTransformer(nn.Module):
         for m in blocks:
             m.set_attn_impl(attn_impl)
         self.attn_impl = attn_impl
+
+    def set_linear_impl(self, linear_impl):
+        """switch every block of a built model between 'torch' and 'hip' (the fused Linears); a block that cannot take it -- its
+        attention is not fused, or a Linear's width is not supported -- raises before any block is switched"""
+        blocks = [m for m in self.modules() if isinstance(m, SwinBlock)]
+        for m in blocks:
+            m.check_linear_impl(linear_impl)
+        for m in blocks:
+            m.set_linear_impl(linear_impl)
+        self.linear_impl = linear_impl
 
     def _to_map(self, out, hw, i, channels_last=False):
         m = out.view(-1, *hw, self.num_features[i]).permute(0, 3, 1, 2)

@@ -2162,3 +2162,90 @@ class SwinWindowAttention(torch.autograd.Function):
         dqkv, dpad, dtable = swin_window_attention_backward(qkv, pad_qkv, bias_table, out, dout, *ctx.cfg, need_pad=need[1],
                                                             need_table=need[2])
         return (dqkv if need[0] else None, None if dpad is None else dpad.to(pad_qkv.dtype), dtable) + (None,) * 6
+
+
+# ------------------------------------------------------------------------------ Swin block Linears (include/preworld_hip_swin_linear.h)
+SWIN_LINEAR_MIN_DIM, SWIN_LINEAR_MAX_DIM = _lib.PW_SWIN_LINEAR['PW_SWIN_LINEAR_MIN_DIM'], _lib.PW_SWIN_LINEAR['PW_SWIN_LINEAR_MAX_DIM']
+_SWIN_LINEAR_DTYPES = {_f32: 'PW_SWIN_F32', torch.bfloat16: 'PW_SWIN_BF16'}
+
+
+class SwinLinearPacked:
+    """the packed operand of one Linear for pw_swin_linear: `buf` (uint8, pw_swin_linear_packed_bytes), K, N and the mode
+    (torch.float32: split-fp16 planes; torch.bfloat16: one bf16 plane)"""
+    __slots__ = ('buf', 'K', 'N', 'dtype')
+
+    def __init__(self, buf, K, N, dtype):
+        self.buf, self.K, self.N, self.dtype = buf, K, N, dtype
+
+
+def swin_linear_supported(K, N):
+    """None if pw_swin_linear takes a Linear with K inputs and N outputs, else the reason it does not"""
+    for what, v in (('in_features', K), ('out_features', N)):
+        if v % 16 or not SWIN_LINEAR_MIN_DIM <= v <= SWIN_LINEAR_MAX_DIM:
+            return '%s %d (supported: multiples of 16 in %d .. %d)' % (what, v, SWIN_LINEAR_MIN_DIM, SWIN_LINEAR_MAX_DIM)
+    return None
+
+
+def swin_linear_pack(weight, bias, ln_weight=None, ln_bias=None, dtype=torch.float32):
+    """Pack nn.Linear's weight (N, K) and bias (N) or None, with the LayerNorm in front of it (ln_weight, ln_bias (K), or neither), for
+    swin_linear in the mode `dtype`: torch.float32 (split-fp16 planes under per-row powers of two) or torch.bfloat16 (weights rounded
+    to bf16).  All inputs are float32 device tensors; gamma and beta are not folded, the packed bias is the Linear's own.  Runs on the
+    device without synchronisation."""
+    fn = 'swin_linear_pack'
+    if dtype not in _SWIN_LINEAR_DTYPES:
+        raise _lib.PreworldHipError('%s: dtype must be torch.float32 or torch.bfloat16, got %s' % (fn, dtype))
+    if weight.dim() != 2:
+        raise _lib.PreworldHipError('%s: weight must be (N, K), got %s' % (fn, tuple(weight.shape)))
+    N, K = weight.shape
+    why = swin_linear_supported(K, N)
+    if why is not None:
+        raise _lib.PreworldHipError('%s: not supported: %s' % (fn, why))
+    if (ln_weight is None) != (ln_bias is None):
+        raise _lib.PreworldHipError('%s: ln_weight and ln_bias come together or not at all' % fn)
+    for name, t, shape in (('weight', weight, (N, K)), ('bias', bias, (N,)), ('ln_weight', ln_weight, (K,)), ('ln_bias', ln_bias, (K,))):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != _f32 or not t.is_contiguous()):
+            raise _lib.PreworldHipError('%s: %s must be a contiguous float32 %s tensor, got %s %s' % (fn, name, shape, t.dtype, tuple(t.shape)))
+    mode = _lib.PW_SWIN[_SWIN_LINEAR_DTYPES[dtype]]
+    nbytes = _lib.call_size('pw_swin_linear_packed_bytes', K, N, mode)
+    if not weight.is_cuda:
+        raise _lib.PreworldHipError('%s: weight must be a CUDA(HIP) tensor' % fn)
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+    _lib.call('pw_swin_linear_pack', weight.detach(), None if bias is None else bias.detach(), None if ln_weight is None else ln_weight.detach(),
+              None if ln_bias is None else ln_bias.detach(), buf, K, N, mode, _lib.STREAM)
+    return SwinLinearPacked(buf, K, N, dtype)
+
+
+def swin_linear(x, packed, *, ln=False, eps=1e-5, act=None, residual=None):
+    """out (.., N) = epi(pro(x (.., K)) W^T + b) in one launch (include/preworld_hip_swin_linear.h): ln=True normalises every row over
+    K first (the packed gamma / beta, biased variance, `eps`); act='gelu' applies the erf GELU; residual (.., N) float32 is added
+    (`residual + y`).  Two launches: the row statistics ((M, 2) floats of workspace), then the GEMM.  packed.dtype float32: x, residual, out float32.  packed.dtype bfloat16 (autocast's data flow): x is float32
+    with ln and bfloat16 without, out is float32 with a residual and bfloat16 without.  Forward only; no workspace, no synchronisation."""
+    fn = 'swin_linear'
+    if not isinstance(packed, SwinLinearPacked):
+        raise _lib.PreworldHipError('%s: packed must come from swin_linear_pack' % fn)
+    if act not in (None, 'gelu'):
+        raise _lib.PreworldHipError("%s: act must be None or 'gelu', got %r" % (fn, act))
+    if act is not None and residual is not None:
+        raise _lib.PreworldHipError('%s: act and residual exclude each other' % fn)
+    K, N, bf = packed.K, packed.N, packed.dtype == torch.bfloat16
+    if x.dim() < 1 or x.shape[-1] != K or x.numel() == 0:
+        raise _lib.PreworldHipError('%s: x must be (.., %d) and not empty, got %s' % (fn, K, tuple(x.shape)))
+    xdt = torch.bfloat16 if bf and not ln else _f32
+    if x.dtype != xdt:
+        raise _lib.PreworldHipError('%s: x must be %s in this mode (packed %s, ln=%s), got %s' % (fn, xdt, packed.dtype, bool(ln), x.dtype))
+    if not x.is_contiguous():
+        raise _lib.PreworldHipError('%s: x must be contiguous' % fn)
+    lead = tuple(x.shape[:-1])
+    if residual is not None and (tuple(residual.shape) != lead + (N,) or residual.dtype != _f32 or not residual.is_contiguous()):
+        raise _lib.PreworldHipError('%s: residual must be a contiguous float32 %s tensor, got %s %s'
+                                    % (fn, lead + (N,), residual.dtype, tuple(residual.shape)))
+    if not x.is_cuda or (residual is not None and not residual.is_cuda) or packed.buf.device != x.device:
+        raise _lib.PreworldHipError('%s: x%s must be a CUDA(HIP) tensor on the device of the packed operand' % (fn, '' if residual is None else ', residual'))
+    out = torch.empty(lead + (N,), device=x.device, dtype=torch.bfloat16 if bf and residual is None else _f32)
+    epi = 'PW_SWIN_LINEAR_EPI_RESIDUAL' if residual is not None else ('PW_SWIN_LINEAR_EPI_GELU' if act == 'gelu' else 'PW_SWIN_LINEAR_EPI_BIAS')
+    M, mode = x.numel() // K, _lib.PW_SWIN[_SWIN_LINEAR_DTYPES[packed.dtype]]
+    nbytes = _lib.call_size('pw_swin_linear_workspace_bytes', M, int(bool(ln)), mode)          # (M, 2) floats of row statistics, or 0
+    wsp = torch.empty(nbytes // 4, device=x.device, dtype=_f32) if nbytes else None
+    _lib.call('pw_swin_linear', x, packed.buf, residual, out, wsp, nbytes, M, K, N, int(bool(ln)), float(eps), _lib.PW_SWIN_LINEAR[epi],
+              mode, _lib.STREAM)
+    return out

@@ -20,7 +20,8 @@ from preworld_amd.pipeline import CapturedSample  # noqa: E402
 
 class ImagePath:
     """the C3 sample's image -> occupancy path, built once: run(amp, attn, steps) times it with the image branch under bf16 autocast
-    or not and the Swin blocks' window attention on the torch path or the fused HIP kernel (attn_impl, preworld_amd/image_encoder.py)"""
+    or not, the Swin blocks' window attention on the torch path or the fused HIP kernel (attn_impl, preworld_amd/image_encoder.py)
+    and their Linears on torch or on the fused HIP GEMM (linear_impl)"""
 
     def __init__(self, dev='cuda:0'):
         T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
@@ -55,9 +56,11 @@ class ImagePath:
     def step(self):
         return self.cap.run(self._f32(self.image_side()), self.ego)
 
-    def run(self, amp='none', attn='torch', steps=10):
+    def run(self, amp='none', attn='torch', steps=10, linear='torch'):
         self.amp = amp
+        self.branch.img_backbone.set_linear_impl('torch')        # 'hip' Linears need a fused attention: switch in an order that holds
         self.branch.img_backbone.set_attn_impl(attn)
+        self.branch.img_backbone.set_linear_impl(linear)
         for _ in range(2):
             self.step()
         torch.cuda.synchronize()
@@ -74,7 +77,7 @@ class ImagePath:
         return {'metric': 'image -> occupancy samples/s (C3, 1 GPU, serial)', 'value': round(1.0 / t_all, 2),
                 'ms_per_sample': round(t_all * 1e3, 2), 'image_branch_ms': round(t_img * 1e3, 2),
                 'voxel_path_ms': round((t_all - t_img) * 1e3, 2), 'image_branch_dtype': 'f32' if amp == 'none' else 'bf16 autocast',
-                'window_attention': attn, 'image_branch_params': self.n_par,
+                'window_attention': attn, 'block_linears': linear, 'image_branch_params': self.n_par,
                 'images': '6 cams x (key + adjacent full backbone, extra reference stage 0), 3x512x1408',
                 'data': 'synthetic, random weights'}
 
@@ -84,8 +87,10 @@ def main():
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--amp', choices=['none', 'bf16'], default='none', help='autocast for the PyTorch image branch only')
     ap.add_argument('--attn', choices=['torch', 'hip'], default='torch', help="the Swin blocks' window attention: torch ops or the fused HIP kernel")
+    ap.add_argument('--linear', choices=['torch', 'hip'], default='torch',
+                    help="the Swin blocks' Linears, LayerNorms, GELU and residuals: torch ops or the fused HIP GEMM (needs --attn hip)")
     a = ap.parse_args()
-    print(json.dumps(ImagePath().run(a.amp, a.attn, a.steps)))
+    print(json.dumps(ImagePath().run(a.amp, a.attn, a.steps, a.linear)))
 
 
 if __name__ == '__main__':
