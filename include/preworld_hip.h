@@ -380,8 +380,10 @@ int pw_render_rays_backward(const float* rays_o, const float* rays_d, int n_rays
  * the worst case n_rays*n_samples*8 (5.1 GB at 38 400 x 417; the forward's count brings it to a few hundred MB).  A bound that turns
  * out too small is a caller bug: nothing is written out of range, grad_grid[0] becomes NaN.
  * Exactness: the fixed-point units leave room for 2^22 largest-magnitude terms per voxel and channel group (a voxel near the cameras
- * sees 10^4..10^5); non-finite upstream gradients are not representable in them and count as 0 (the float-atomics entry point
- * propagates them). */
+ * sees 10^4..10^5); non-finite upstream gradients are not representable in them: when the recorded max |d sigma * corner weight|
+ * or g_absmax is NaN / Inf, grad_grid[0] (and every long voxel's channels) becomes NaN and the rest of the grid is meaningless --
+ * the float-atomics entry point and the reference's autograd propagate them, and a caller that skips a step on a non-finite
+ * gradient norm must see them here too.  Finite inputs: bit for bit the result without this rule. */
 size_t pw_render_backward_workspace_bytes(int n_rays, int n_samples, int X, int Y, int Z, int64_t max_entries);
 int pw_render_rays_backward_sorted(const float* rays_o, const float* rays_d, int n_rays, const float* t, int n_samples,
                                    const float* grid, int X, int Y, int Z, int grid_channels, int c_sigma, int c_sem,

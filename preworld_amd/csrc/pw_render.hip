@@ -823,12 +823,19 @@ __global__ void __launch_bounds__(256) k_rb_gather_long(RbArgs a) {
 __global__ void __launch_bounds__(256) k_rb_finish_long(RbArgs a) {
   const int nl = min(a.head[2], a.max_long);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  // the caller's entry bound was too small (a bug, not a data condition): no partial gradient passes for a result
-  if (i == 0 && a.head[4]) a.grad_grid[0] = __uint_as_float(0x7fc00000u);
+  // the caller's entry bound was too small (a bug, not a data condition): no partial gradient passes for a result.  Nor does one
+  // computed from a non-finite upstream gradient: a NaN / Inf in g_depth, g_last or g_weights reaches the recorded max |b|, one in
+  // g_sem / g_rgb the caller's max |g|; rb_scale then returns 1 and __double2ll_rn turns the NaN terms into finite integers, so the
+  // sums above are finite and wrong.  The float-atomic form and the reference's autograd propagate the NaN; here the result is
+  // poisoned the same way as for an overflow (every thread that owns an element writes NaN too, so no += can lose the poison).
+  const float bmax = __uint_as_float((unsigned)a.head[1]), gmax = *a.gmax;
+  const bool poison = a.head[4] != 0 || !(bmax <= 3.4028235e38f) || !(fabsf(gmax) <= 3.4028235e38f);
+  if (i == 0 && poison) a.grad_grid[0] = __uint_as_float(0x7fc00000u);
   if (i >= nl * RB_CH) return;
   const int li = i / RB_CH, ch = i - li * RB_CH;
-  const double sc = ch == 0 ? rb_scale(__uint_as_float((unsigned)a.head[1])) : rb_scale(*a.gmax);
-  a.grad_grid[(size_t)a.long_list[li] * a.GC + rb_channel_index(a, ch)] += (float)((double)a.long_acc[i] / sc);
+  const double sc = ch == 0 ? rb_scale(bmax) : rb_scale(gmax);
+  const float add = (float)((double)a.long_acc[i] / sc);
+  a.grad_grid[(size_t)a.long_list[li] * a.GC + rb_channel_index(a, ch)] += poison ? __uint_as_float(0x7fc00000u) : add;
 }
 
 // entries the arrays are laid out for: the caller's bound when it gives one, else every sample of every ray with 8 in-bounds corners
