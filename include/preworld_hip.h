@@ -805,6 +805,8 @@ int pw_copy_many(const void* const* src, void* const* dst, const size_t* bytes, 
 
 /* The Swin blocks' Linears with LayerNorm, GELU and residual fused in (pw_swin_linear*) are declared in preworld_hip_swin_linear.h. */
 #include "preworld_hip_swin_linear.h"
+/* Their gradient (pw_swin_linear_backward_*, pw_swin_layernorm_backward) is declared in preworld_hip_swin_linear_bwd.h. */
+#include "preworld_hip_swin_linear_bwd.h"
 
 #ifdef __cplusplus
 }

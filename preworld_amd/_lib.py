@@ -34,6 +34,7 @@ RAYS_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip_rays.h')  
 SWIN_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip_swin.h')        # ... and the Swin window attention (pw_swin_*)
 SWIN_BWD_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip_swin_bwd.h')      # ... and its gradient
 SWIN_LINEAR_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip_swin_linear.h')      # ... and the Swin blocks' fused Linears
+SWIN_LINEAR_BWD_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip_swin_linear_bwd.h')      # ... and their gradient
 
 _CTYPES = {
     'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64,
@@ -162,6 +163,8 @@ _swin_bwd_protos, PW_SWIN_BWD = _parse(SWIN_BWD_HEADER_PATH)      # ... and thos
 _protos.update(_swin_bwd_protos)
 _swin_linear_protos, PW_SWIN_LINEAR = _parse(SWIN_LINEAR_HEADER_PATH)      # ... and those of the fused Linears (PW_SWIN_LINEAR_*)
 _protos.update(_swin_linear_protos)
+_swin_linear_bwd_protos, PW_SWIN_LINEAR_BWD = _parse(SWIN_LINEAR_BWD_HEADER_PATH)      # ... and those of their gradient (PW_SWIN_LINEAR_BWD_*)
+_protos.update(_swin_linear_bwd_protos)
 _lib = None
 _fns = {}
 

@@ -6,7 +6,8 @@ attn_impl='hip', the Swin blocks' shifted-window attention (ops.swin_window_atte
 and proj Linears -- DESIGN.md 17; forward only, the default 'torch' path is unchanged; attn_impl='hip_grad' adds the kernel's
 HIP backward, ops.swin_window_attention_backward -- DESIGN.md 17b) and, with linear_impl='hip' on top of a fused attention, the
 blocks' four Linears with both LayerNorms, the GELU and both residual additions fused in (ops.swin_linear, five calls per block
--- DESIGN.md 17c; forward only, the default 'torch' is unchanged).
+-- DESIGN.md 17c; forward only, the default 'torch' is unchanged; linear_impl='hip_grad' on top of attn_impl='hip_grad' adds their
+HIP backward, ops.SwinLinear / ops.swin_linear_backward -- DESIGN.md 17d).
 
 State-dict keys, constructor arguments and forward contracts are the reference's, so released checkpoints load:
 
@@ -83,17 +84,20 @@ def _check_attn_impl(attn_impl, embed_dims, num_heads, ws):
     return attn_impl
 
 
-LINEAR_IMPLS = ('torch', 'hip')
+LINEAR_IMPLS = ('torch', 'hip', 'hip_grad')
 
 
 def _check_linear_impl(linear_impl, attn_impl, embed_dims, feedforward_channels):
-    """'hip' has no fallback: it needs the fused attention (the block hands the kernel its qkv directly) and Linears that
-    pw_swin_linear takes, and is refused otherwise where the module is built"""
+    """'hip' and 'hip_grad' have no fallback: they need the fused attention (the block hands the kernel its qkv directly; 'hip_grad'
+    needs attn_impl 'hip_grad', whose backward it is composed with) and Linears that pw_swin_linear takes, and are refused otherwise
+    where the module is built"""
     if linear_impl not in LINEAR_IMPLS:
         raise ValueError('linear_impl must be one of %s, got %r' % (LINEAR_IMPLS, linear_impl))
     if linear_impl != 'torch':
         if attn_impl not in ('hip', 'hip_grad'):
             raise ValueError("linear_impl=%r needs attn_impl 'hip' or 'hip_grad', got %r" % (linear_impl, attn_impl))
+        if linear_impl == 'hip_grad' and attn_impl != 'hip_grad':
+            raise ValueError("linear_impl='hip_grad' needs attn_impl 'hip_grad', got %r" % (attn_impl,))
         from . import ops
         for K, N in ((embed_dims, 3 * embed_dims), (embed_dims, embed_dims), (embed_dims, feedforward_channels),
                      (feedforward_channels, embed_dims)):
@@ -265,7 +269,13 @@ class SwinBlock(nn.Module):
     would need a backward the block runs exactly what linear_impl='torch' runs.  An fp32 block runs the split-fp16 mode, under
     torch.autocast(bfloat16) the bf16 mode; a block whose residual stream is not float32 (.bfloat16(), .half()) is refused.  The
     packed operands live in a modules.Derived cache keyed on the Linears' and LayerNorms' parameters; parameters, buffers and
-    state-dict keys do not depend on linear_impl."""
+    state-dict keys do not depend on linear_impl.
+    linear_impl='hip_grad' (needs attn_impl 'hip_grad'): without grad exactly 'hip'.  With grad in float32 the same five calls run as
+    autograd Functions (ops.SwinLinear around ops.swin_linear, ops.SwinWindowAttention): the forward gives the same bits, the backward
+    is include/preworld_hip_swin_linear_bwd.h, and the torch Linears, LayerNorms and GELU never run.  Saved per token are x, qkv, the
+    attention output, x1 and the hidden tensor (10 C; neither LayerNorm output nor the pre-GELU tensor).  Under bf16 autocast with
+    grad it does what 'hip' does (the torch path): the gradient kernels are float32 only.  There is no DropPath in this block (as
+    with attn_impl='hip_grad'), so none is fused."""
 
     def __init__(self, embed_dims, num_heads, feedforward_channels, window_size, shift, qkv_bias=True, qk_scale=None,
                  attn_impl='torch', linear_impl='torch'):
@@ -329,9 +339,45 @@ class SwinBlock(nn.Module):
         h = ops.swin_linear(x, fc1_p, ln=True, eps=self.norm2.eps, act='gelu')
         return ops.swin_linear(h, fc2_p, residual=x)
 
+    def _packed_t(self):
+        """(qkv, proj, fc1, fc2) transposed packs for the data gradient: same sources as _packed, so an in-place optimizer step
+        rebuilds them with the forward packs"""
+        from . import ops
+        from .modules import Derived
+        if self._derived is None:
+            self._derived = Derived()
+        m, fc1, fc2 = self.attn.w_msa, self.ffn.layers[0][0], self.ffn.layers[1]
+        return self._derived.get('swin_linear_t_%s' % torch.float32, (self.norm1, m.qkv, m.proj, self.norm2, fc1, fc2),
+                                 lambda: tuple(ops.swin_linear_pack_transposed(l.weight) for l in (m.qkv, m.proj, fc1, fc2)))
+
+    def _forward_fused_grad(self, x, hw_shape):
+        """float32 with grad: the five calls of _forward_fused as autograd Functions (ops.SwinLinear, ops.SwinWindowAttention).  The
+        residual additions go through SwinLinear's pass-through output, so every gradient of the residual stream is folded into a
+        kernel and autograd adds only the two small contributions to qkv.bias (dpad and the column sums of dqkv)."""
+        from . import _lib, ops
+        m, fc1, fc2 = self.attn.w_msa, self.ffn.layers[0][0], self.ffn.layers[1]
+        params = [p for mod in (self.norm1, m.qkv, m.proj, self.norm2, self.ffn) for p in mod.parameters()]
+        if x.dtype != torch.float32 or any(p.dtype != torch.float32 for p in params):
+            raise _lib.PreworldHipError("SwinBlock(linear_impl='hip_grad'): the residual stream and the parameters must be float32 (got x %s)"
+                                        % x.dtype)
+        qkv_p, proj_p, fc1_p, fc2_p = self._packed(torch.float32)
+        qkv_t, proj_t, fc1_t, fc2_t = self._packed_t()
+        if not x.is_contiguous():
+            x = x.contiguous()
+        L = ops.SwinLinear.apply
+        qkv, x = L(x, m.qkv.weight, m.qkv.bias, self.norm1.weight, self.norm1.bias, None, qkv_p, qkv_t, 'ln', self.norm1.eps)
+        a = ops.SwinWindowAttention.apply(qkv, m.qkv.bias, m.relative_position_bias_table, hw_shape[0], hw_shape[1], m.num_heads,
+                                          self.attn.window_size, self.attn.shift_size, m.scale)
+        x = L(a, m.proj.weight, m.proj.bias, None, None, x, proj_p, proj_t, 'res', 0.0)
+        h, x = L(x, fc1.weight, fc1.bias, self.norm2.weight, self.norm2.bias, None, fc1_p, fc1_t, 'ln_gelu', self.norm2.eps)
+        return L(h, fc2.weight, fc2.bias, None, None, x, fc2_p, fc2_t, 'res', 0.0)
+
     def forward(self, x, hw_shape):
-        if self.linear_impl == 'hip' and not self._needs_backward(x):
-            return self._forward_fused(x, hw_shape)
+        if self.linear_impl != 'torch':
+            if not self._needs_backward(x):
+                return self._forward_fused(x, hw_shape)
+            if self.linear_impl == 'hip_grad' and not torch.is_autocast_enabled('cuda'):
+                return self._forward_fused_grad(x, hw_shape)
         x = self.attn(self.norm1(x), hw_shape) + x
         return self.ffn(self.norm2(x), identity=x)
 
@@ -357,8 +403,8 @@ class SwinTransformer(nn.Module):
     """Same constructor arguments as the reference (those that only matter for training / checkpoint loading are
     accepted and ignored), plus attn_impl: 'torch' (default), 'hip', the fused window attention of ShiftWindowMSA (forward only), or
     'hip_grad', the same with its HIP backward; a config selects one with dict(type='SwinTransformer', ..., attn_impl='hip'); and
-    linear_impl: 'torch' (default) or 'hip', the blocks' Linears with LayerNorm, GELU and residual fused in (SwinBlock; needs a fused
-    attn_impl).  forward(x (BN,3,H,W)) -> list: [stage-0 feature un-normed if return_stereo_feat] +
+    linear_impl: 'torch' (default), 'hip', the blocks' Linears with LayerNorm, GELU and residual fused in (SwinBlock; needs a fused
+    attn_impl; forward only), or 'hip_grad', the same with their HIP backward (needs attn_impl='hip_grad').  forward(x (BN,3,H,W)) -> list: [stage-0 feature un-normed if return_stereo_feat] +
     [norm_i(stage i) for i in out_indices], each (BN, C_i, H_i, W_i) -- swin.py:946-971."""
 
     def __init__(self, pretrain_img_size=224, in_channels=3, embed_dims=96, patch_size=4, window_size=7, mlp_ratio=4,
@@ -401,7 +447,7 @@ class SwinTransformer(nn.Module):
         self.attn_impl = attn_impl
 
     def set_linear_impl(self, linear_impl):
-        """switch every block of a built model between 'torch' and 'hip' (the fused Linears); a block that cannot take it -- its
+        """switch every block of a built model between 'torch', 'hip' and 'hip_grad' (the fused Linears); a block that cannot take it -- its
         attention is not fused, or a Linear's width is not supported -- raises before any block is switched"""
         blocks = [m for m in self.modules() if isinstance(m, SwinBlock)]
         for m in blocks:

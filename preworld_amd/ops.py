@@ -2249,3 +2249,217 @@ def swin_linear(x, packed, *, ln=False, eps=1e-5, act=None, residual=None):
     _lib.call('pw_swin_linear', x, packed.buf, residual, out, wsp, nbytes, M, K, N, int(bool(ln)), float(eps), _lib.PW_SWIN_LINEAR[epi],
               mode, _lib.STREAM)
     return out
+
+
+# ------------------------------------------------------------------------ their gradient (include/preworld_hip_swin_linear_bwd.h)
+SWIN_LINEAR_ROLES = ('ln', 'ln_gelu', 'res')      # Linear(LayerNorm(x)); GELU(Linear(LayerNorm(x))); residual + Linear(x)
+
+
+def _swin_bwd_f32(fn, **tensors):
+    """every named tensor (None is skipped) is a contiguous float32 CUDA(HIP) tensor on one device"""
+    dev = None
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        if t.dtype != _f32 or not t.is_contiguous():
+            raise _lib.PreworldHipError('%s: %s must be a contiguous float32 tensor, got %s %s' % (fn, name, t.dtype, tuple(t.shape)))
+        if not t.is_cuda or (dev is not None and t.device != dev):
+            raise _lib.PreworldHipError('%s: %s must be a CUDA(HIP) tensor on the device of the other operands' % (fn, name))
+        dev = t.device
+
+
+def _swin_bwd_packed(fn, packed, name='packed'):
+    if not isinstance(packed, SwinLinearPacked):
+        raise _lib.PreworldHipError('%s: %s must come from swin_linear_pack / swin_linear_pack_transposed' % (fn, name))
+    if packed.dtype != _f32:
+        raise _lib.PreworldHipError('%s: the gradient is float32 only, %s is packed for %s' % (fn, name, packed.dtype))
+
+
+def _swin_bwd_rows(fn, t, name, width):
+    if t.dim() < 1 or t.shape[-1] != width or t.numel() == 0:
+        raise _lib.PreworldHipError('%s: %s must be (.., %d) and not empty, got %s' % (fn, name, width, tuple(t.shape)))
+    return t.numel() // width
+
+
+def swin_linear_pack_transposed(weight):
+    """nn.Linear's weight (N, K), float32 on the device -> W^T packed as the weight of swin_linear_backward_data: a SwinLinearPacked
+    with N inputs and K outputs (the columns of W as rows, each under its own power of two; zero bias, no LayerNorm)."""
+    fn = 'swin_linear_pack_transposed'
+    if weight.dim() != 2:
+        raise _lib.PreworldHipError('%s: weight must be (N, K), got %s' % (fn, tuple(weight.shape)))
+    N, K = weight.shape
+    why = swin_linear_supported(K, N)
+    if why is not None:
+        raise _lib.PreworldHipError('%s: not supported: %s' % (fn, why))
+    _swin_bwd_f32(fn, weight=weight)
+    nbytes = _lib.call_size('pw_swin_linear_backward_packed_bytes', K, N)
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+    _lib.call('pw_swin_linear_backward_pack', weight.detach(), buf, K, N, _lib.STREAM)
+    return SwinLinearPacked(buf, N, K, _f32)
+
+
+def swin_linear_backward_data(g, packed_t):
+    """dx (.., K) = g (.., N) W, the forward GEMM with swin_linear_pack_transposed's operand as its weight (two launches)"""
+    fn = 'swin_linear_backward_data'
+    _swin_bwd_packed(fn, packed_t, 'packed_t')
+    N, K = packed_t.K, packed_t.N                       # the transposed operand has N inputs and K outputs
+    M = _swin_bwd_rows(fn, g, 'g', N)
+    _swin_bwd_f32(fn, g=g)
+    if not g.is_cuda or packed_t.buf.device != g.device:
+        raise _lib.PreworldHipError('%s: g must be a CUDA(HIP) tensor on the device of the packed operand' % fn)
+    dx = torch.empty(tuple(g.shape[:-1]) + (K,), device=g.device, dtype=_f32)
+    nbytes = _lib.call_size('pw_swin_linear_backward_rows_workspace_bytes', M)
+    wsp = torch.empty(nbytes // 4, device=g.device, dtype=_f32)
+    _lib.call('pw_swin_linear_backward_data', g, packed_t.buf, dx, wsp, nbytes, M, K, N, _lib.STREAM)
+    return dx
+
+
+def swin_linear_backward_gelu(x, packed, dh, eps=1e-5, out=None):
+    """dz (.., N) = dh o gelu'(LayerNorm(x) W^T + b): the fc1 forward GEMM with the GELU gradient as its epilogue; the pre-activation
+    is recomputed and never stored.  out=dh writes dz over dh."""
+    fn = 'swin_linear_backward_gelu'
+    _swin_bwd_packed(fn, packed)
+    K, N = packed.K, packed.N
+    M = _swin_bwd_rows(fn, x, 'x', K)
+    if tuple(dh.shape) != tuple(x.shape[:-1]) + (N,):
+        raise _lib.PreworldHipError('%s: dh must be %s, got %s' % (fn, tuple(x.shape[:-1]) + (N,), tuple(dh.shape)))
+    if out is not None and tuple(out.shape) != tuple(dh.shape):
+        raise _lib.PreworldHipError('%s: out must have the shape of dh' % fn)
+    _swin_bwd_f32(fn, x=x, dh=dh, out=out)
+    if not x.is_cuda or packed.buf.device != x.device:
+        raise _lib.PreworldHipError('%s: x must be a CUDA(HIP) tensor on the device of the packed operand' % fn)
+    dz = torch.empty_like(dh) if out is None else out
+    nbytes = _lib.call_size('pw_swin_linear_backward_rows_workspace_bytes', M)
+    wsp = torch.empty(nbytes // 4, device=x.device, dtype=_f32)
+    _lib.call('pw_swin_linear_backward_gelu', x, packed.buf, dh, dz, wsp, nbytes, M, K, N, float(eps), _lib.STREAM)
+    return dz
+
+
+def swin_linear_backward_weight(g, x, packed=None, *, ln=False, eps=1e-5, need_weight=True, need_bias=True):
+    """(dweight (N, K) = g^T pro(x), dbias (N) = column sums of g) for g (.., N), x (.., K); pro = LayerNorm with the gamma / beta of
+    `packed` (the forward's operand) when ln, identity otherwise.  A gradient that is not needed is None and its work is skipped."""
+    fn = 'swin_linear_backward_weight'
+    if not (need_weight or need_bias):
+        return None, None
+    if ln:
+        _swin_bwd_packed(fn, packed)
+    if g.dim() < 1 or x.dim() < 1 or tuple(g.shape[:-1]) != tuple(x.shape[:-1]) or g.numel() == 0:
+        raise _lib.PreworldHipError('%s: g (.., N) and x (.., K) must share their leading dimensions, got %s and %s' % (fn, tuple(g.shape), tuple(x.shape)))
+    K, N = x.shape[-1], g.shape[-1]
+    if ln and (packed.K, packed.N) != (K, N):
+        raise _lib.PreworldHipError('%s: packed is a (%d -> %d) Linear, g and x say (%d -> %d)' % (fn, packed.K, packed.N, K, N))
+    why = swin_linear_supported(K, N)
+    if why is not None:
+        raise _lib.PreworldHipError('%s: not supported: %s' % (fn, why))
+    _swin_bwd_f32(fn, g=g, x=x)
+    if ln and packed.buf.device != g.device:
+        raise _lib.PreworldHipError('%s: g must be on the device of the packed operand' % fn)
+    M = g.numel() // N
+    dw = torch.empty(N, K, device=g.device, dtype=_f32) if need_weight else None
+    db = torch.empty(N, device=g.device, dtype=_f32) if need_bias else None
+    nbytes = _lib.call_size('pw_swin_linear_backward_weight_workspace_bytes', M, K, N, int(bool(ln)))
+    wsp = torch.empty(nbytes // 8, device=g.device, dtype=torch.float64)
+    _lib.call('pw_swin_linear_backward_weight', g, x, packed.buf if ln else None, dw, db, wsp, nbytes, M, K, N, int(bool(ln)), float(eps),
+              _lib.STREAM)
+    return dw, db
+
+
+def swin_layernorm_backward(dxn, x, gamma, dres=None, *, eps=1e-5, need_x=True, need_affine=True, out=None):
+    """Gradient of LayerNorm(x) over the last dimension for dxn: (dx = dres + ..., dgamma, dbeta); dres (like x) or None is the
+    residual stream's own gradient, folded in.  need_x / need_affine False skip that part (None).  out=dxn writes dx over dxn."""
+    fn = 'swin_layernorm_backward'
+    if not (need_x or need_affine):
+        return None, None, None
+    K = x.shape[-1] if x.dim() else 0
+    why = swin_linear_supported(K, K) if K else 'empty x'
+    if why is not None:
+        raise _lib.PreworldHipError('%s: not supported: %s' % (fn, why))
+    M = _swin_bwd_rows(fn, x, 'x', K)
+    for name, t in (('dxn', dxn), ('dres', dres), ('out', out)):
+        if t is not None and tuple(t.shape) != tuple(x.shape):
+            raise _lib.PreworldHipError('%s: %s must have the shape of x %s, got %s' % (fn, name, tuple(x.shape), tuple(t.shape)))
+    if tuple(gamma.shape) != (K,):
+        raise _lib.PreworldHipError('%s: gamma must be (%d,), got %s' % (fn, K, tuple(gamma.shape)))
+    _swin_bwd_f32(fn, dxn=dxn, x=x, gamma=gamma, dres=dres, out=out)
+    dx = (torch.empty_like(x) if out is None else out) if need_x else None
+    dg = torch.empty(K, device=x.device, dtype=_f32) if need_affine else None
+    db = torch.empty(K, device=x.device, dtype=_f32) if need_affine else None
+    nbytes = _lib.call_size('pw_swin_layernorm_backward_workspace_bytes', M, K)
+    wsp = torch.empty(nbytes // 8, device=x.device, dtype=torch.float64)
+    _lib.call('pw_swin_layernorm_backward', dxn, x, gamma.detach(), dres if need_x else None, dx, dg, db, wsp, nbytes, M, K, float(eps),
+              _lib.STREAM)
+    return dx, dg, db
+
+
+def swin_linear_backward(role, g, x, packed, packed_t=None, *, gamma=None, eps=1e-5, dres=None, need_x=True, need_weight=True,
+                         need_bias=True, need_ln=True):
+    """The gradient of one role of swin_linear for the cotangent g of its output: (dx, dweight, dbias, dgamma, dbeta).
+    'res': dx = g W, dweight = g^T x, dbias = column sums of g (the residual's gradient is g itself).
+    'ln' / 'ln_gelu': gy = g or g o gelu'(y); dweight = gy^T LayerNorm(x), dbias; dx = dres + LayerNorm'(gy W), dgamma, dbeta.
+    packed is the forward's operand, packed_t swin_linear_pack_transposed's (needed for dx, dgamma, dbeta), gamma the LayerNorm's
+    weight.  A gradient whose need_* is False is None and its launches are skipped."""
+    fn = 'swin_linear_backward'
+    if role not in SWIN_LINEAR_ROLES:
+        raise _lib.PreworldHipError('%s: role must be one of %s, got %r' % (fn, SWIN_LINEAR_ROLES, role))
+    _swin_bwd_packed(fn, packed)
+    ln = role != 'res'
+    need_ln = need_ln and ln
+    if not (need_x or need_weight or need_bias or need_ln):
+        return None, None, None, None, None
+    if (need_x or need_ln) and packed_t is None:
+        raise _lib.PreworldHipError('%s: dx, dgamma and dbeta need packed_t' % fn)
+    if (need_x or need_ln) and ln and gamma is None:
+        raise _lib.PreworldHipError('%s: role %r needs gamma' % (fn, role))
+    if not g.is_contiguous():
+        g = g.contiguous()
+    gy = swin_linear_backward_gelu(x, packed, g, eps) if role == 'ln_gelu' else g
+    dw, db = swin_linear_backward_weight(gy, x, packed, ln=ln, eps=eps, need_weight=need_weight, need_bias=need_bias)
+    dx = dg = dbeta = None
+    if need_x or need_ln:
+        dxn = swin_linear_backward_data(gy, packed_t)
+        if ln:
+            dx, dg, dbeta = swin_layernorm_backward(dxn, x, gamma, dres, eps=eps, need_x=need_x, need_affine=need_ln, out=dxn)
+        else:
+            dx = dxn
+    return dx, dw, db, dg, dbeta
+
+
+class SwinLinear(torch.autograd.Function):
+    """swin_linear with swin_linear_backward as its gradient, float32 only: apply(x, weight, bias or None, gamma, beta (None for 'res'),
+    residual (None unless 'res'), packed, packed_t, role, eps).  The forward is the same swin_linear call, so the same bits.  Role
+    'res' returns out.  Roles 'ln' and 'ln_gelu' return (out, x): the second output is x itself, for the residual addition behind
+    the Linear -- its gradient comes back here and is folded into the LayerNorm's gradient, so autograd adds nothing.  Saved are x
+    and the (small) parameters; the residual is not needed, the normalised tokens and the pre-GELU tensor are recomputed."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, residual, packed, packed_t, role, eps):
+        if role not in SWIN_LINEAR_ROLES:
+            raise _lib.PreworldHipError('SwinLinear: role must be one of %s, got %r' % (SWIN_LINEAR_ROLES, role))
+        _swin_bwd_packed('SwinLinear', packed)
+        ln = role != 'res'
+        if ln != (gamma is not None) or ln != (beta is not None) or ln == (residual is not None):
+            raise _lib.PreworldHipError("SwinLinear: gamma and beta go with the roles 'ln' and 'ln_gelu', residual with 'res'")
+        out = swin_linear(x, packed, ln=ln, eps=eps, act='gelu' if role == 'ln_gelu' else None, residual=residual)
+        ctx.save_for_backward(x, gamma)
+        ctx.cfg = (role, eps, packed, packed_t)
+        ctx.set_materialize_grads(False)               # an unused output's gradient arrives as None, not as a tensor of zeros
+        return (out, x) if ln else out
+
+    @staticmethod
+    def backward(ctx, g, dres=None):
+        x, gamma = ctx.saved_tensors
+        role, eps, packed, packed_t = ctx.cfg
+        need = ctx.needs_input_grad
+        if g is None:                                  # only the pass-through x was used
+            return (dres if need[0] else None,) + (None,) * 9
+        shape = g.shape
+        if dres is not None and not dres.is_contiguous():
+            dres = dres.contiguous()
+        if not g.is_contiguous():
+            g = g.contiguous()
+        dx, dw, db, dg, dbeta = swin_linear_backward(role, g, x, packed, packed_t, gamma=gamma, eps=eps, dres=dres, need_x=need[0],
+                                                     need_weight=need[1], need_bias=need[2], need_ln=need[3] or need[4])
+        if need[0] and dx is None:
+            dx = dres
+        dresidual = g.view(shape) if role == 'res' and need[5] else None
+        return (dx, dw, db, dg if need[3] else None, dbeta if need[4] else None, dresidual, None, None, None, None)
