@@ -808,6 +808,10 @@ int pw_copy_many(const void* const* src, void* const* dst, const size_t* bytes, 
 /* Their gradient (pw_swin_linear_backward_*, pw_swin_layernorm_backward) is declared in preworld_hip_swin_linear_bwd.h. */
 #include "preworld_hip_swin_linear_bwd.h"
 
+/* The stride-1 convolutions of FPN_LSS and DepthNet with BatchNorm, bias, ReLU and residual fused in (pw_conv2d*) are declared in
+ * preworld_hip_conv2d.h. */
+#include "preworld_hip_conv2d.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,7 @@ SWIN_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip_swin.h')  
 SWIN_BWD_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip_swin_bwd.h')      # ... and its gradient
 SWIN_LINEAR_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip_swin_linear.h')      # ... and the Swin blocks' fused Linears
 SWIN_LINEAR_BWD_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip_swin_linear_bwd.h')      # ... and their gradient
+CONV2D_HEADER_PATH = os.path.join(_HERE, '..', 'include', 'preworld_hip_conv2d.h')      # ... and the FPN_LSS / DepthNet convolutions (pw_conv2d*)
 
 _CTYPES = {
     'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64,
@@ -165,6 +166,8 @@ _swin_linear_protos, PW_SWIN_LINEAR = _parse(SWIN_LINEAR_HEADER_PATH)      # ...
 _protos.update(_swin_linear_protos)
 _swin_linear_bwd_protos, PW_SWIN_LINEAR_BWD = _parse(SWIN_LINEAR_BWD_HEADER_PATH)      # ... and those of their gradient (PW_SWIN_LINEAR_BWD_*)
 _protos.update(_swin_linear_bwd_protos)
+_conv2d_protos, PW_CONV2D = _parse(CONV2D_HEADER_PATH)     # ... and those of the image side's fused convolutions (PW_CONV2D_*)
+_protos.update(_conv2d_protos)
 _lib = None
 _fns = {}
 

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(CSRC, 'libpreworld_hip.so')
 ARCH = 'gfx950'
 ABI_HEADERS = ('preworld_hip.h', 'preworld_hip_optim.h', 'preworld_hip_rays.h', 'preworld_hip_swin.h',
-               'preworld_hip_swin_bwd.h', 'preworld_hip_swin_linear.h', 'preworld_hip_swin_linear_bwd.h')      # include/: hashed, and every object depends on them
+               'preworld_hip_swin_bwd.h', 'preworld_hip_swin_linear.h', 'preworld_hip_swin_linear_bwd.h', 'preworld_hip_conv2d.h')      # include/: hashed, and every object depends on them
 
 COMMON = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-fvisibility=hidden',
           '-Wall', '-Wno-unused-function', '-fno-gpu-rdc']

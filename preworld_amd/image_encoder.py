@@ -7,7 +7,9 @@ and proj Linears -- DESIGN.md 17; forward only, the default 'torch' path is unch
 HIP backward, ops.swin_window_attention_backward -- DESIGN.md 17b) and, with linear_impl='hip' on top of a fused attention, the
 blocks' four Linears with both LayerNorms, the GELU and both residual additions fused in (ops.swin_linear, five calls per block
 -- DESIGN.md 17c; forward only, the default 'torch' is unchanged; linear_impl='hip_grad' on top of attn_impl='hip_grad' adds their
-HIP backward, ops.SwinLinear / ops.swin_linear_backward -- DESIGN.md 17d).
+HIP backward, ops.SwinLinear / ops.swin_linear_backward -- DESIGN.md 17d).  With conv_impl='hip' on FPN_LSS / DepthNet /
+ImageBranch a fourth: their stride-1 convolutions with BatchNorm, bias, ReLU and residual fused in (ops.conv2d, one implicit GEMM per
+layer over channels-last maps -- DESIGN.md 17e; float32, eval mode and forward only, the default 'torch' is unchanged).
 
 State-dict keys, constructor arguments and forward contracts are the reference's, so released checkpoints load:
 
@@ -484,10 +486,90 @@ class SwinTransformer(nn.Module):
         return self._to_map(out, out_hw, 0, channels_last=True)
 
 
+# ----------------------------------------------------------------------------------------------- fused convolutions
+CONV_IMPLS = ('torch', 'hip')
+
+
+def _conv_reason(conv):
+    """None if ops.conv2d takes this layer, else the reason it does not"""
+    from . import ops
+    if not isinstance(conv, nn.Conv2d):
+        return 'a %s is not an nn.Conv2d' % type(conv).__name__
+    if conv.padding_mode != 'zeros':
+        return 'padding_mode %r' % conv.padding_mode
+    return ops.conv2d_supported(conv.in_channels, conv.out_channels, conv.kernel_size, conv.stride, conv.dilation, conv.padding,
+                                conv.groups)
+
+
+def _check_conv_impl(conv_impl, convs):
+    """'hip' has no fallback: a layer pw_conv2d does not take is refused where the module is built or switched"""
+    if conv_impl not in CONV_IMPLS:
+        raise ValueError('conv_impl must be one of %s, got %r' % (CONV_IMPLS, conv_impl))
+    if conv_impl != 'torch':
+        for name, conv in convs:
+            why = _conv_reason(conv)
+            if why is not None:
+                raise ValueError("conv_impl=%r: the fused convolution does not support %s: %s" % (conv_impl, name, why))
+    return conv_impl
+
+
+def _channels_last(x):
+    """x in torch.channels_last storage: itself if it already is, else one copy"""
+    return x if x.permute(0, 2, 3, 1).is_contiguous() else x.contiguous(memory_format=torch.channels_last)
+
+
+class _FusedConvs:
+    """What FPN_LSS, DepthNet, BasicBlock2d, ASPP and _ASPPModule share for conv_impl='hip': every stride-1 convolution listed by
+    _own_convs() runs ops.conv2d (include/preworld_hip_conv2d.h) with its eval-mode BatchNorm, bias, ReLU and residual folded in, on
+    channels-last maps.  The fused path is taken in eval mode, when autograd needs no backward, outside autocast; in training mode
+    (BatchNorm batch statistics), with grad, or under autocast (bf16) the module runs exactly its 'torch' path -- those are out of
+    scope of the kernel.  Packed operands live in a modules.Derived cache keyed on the convolution's parameters and the BatchNorm's
+    parameters and running statistics, so load_state_dict or an optimizer step rebuilds them.  Parameters, buffers and state-dict
+    keys do not depend on conv_impl."""
+    conv_impl = 'torch'
+    _derived = None
+
+    def _own_convs(self):
+        raise NotImplementedError
+
+    def _fused_convs(self):
+        """(name, layer) of every convolution the fused path of this module and of the modules below it runs"""
+        return [((prefix + '.' if prefix else '') + n, c) for prefix, m in self.named_modules() if isinstance(m, _FusedConvs)
+                for n, c in m._own_convs()]
+
+    def check_conv_impl(self, conv_impl):
+        return _check_conv_impl(conv_impl, self._fused_convs())
+
+    def set_conv_impl(self, conv_impl):
+        """switch this module and every module below it between 'torch' and 'hip'; a layer the kernel does not take raises before any
+        module is switched"""
+        self.check_conv_impl(conv_impl)
+        for m in self.modules():
+            if isinstance(m, _FusedConvs):
+                m.conv_impl = conv_impl
+
+    def _fused(self, *xs):
+        if self.conv_impl != 'hip' or self.training or torch.is_autocast_enabled(xs[0].device.type):
+            return False
+        return not (torch.is_grad_enabled() and (any(x.requires_grad for x in xs) or any(p.requires_grad for p in self.parameters())))
+
+    def _conv(self, x, name, conv, bn=None, relu=False, residual=None):
+        from . import ops
+        from .modules import Derived
+        if self._derived is None:
+            self._derived = Derived()
+        pk = self._derived.get('conv2d_' + name, (conv, bn), lambda: ops.conv2d_pack(conv, bn))
+        return ops.conv2d(x, pk, dilation=conv.dilation[0], relu=relu, residual=residual)
+
+
 # ----------------------------------------------------------------------------------------------- FPN_LSS
-class FPN_LSS(nn.Module):
+class FPN_LSS(_FusedConvs, nn.Module):
+    """lss_fpn.py:12-101.  conv_impl='torch' (default) or 'hip' (_FusedConvs): with 'hip' the inputs are made channels-last, the
+    bilinear upsample and the concat stay on torch, and the convolutions run ops.conv2d with BatchNorm and ReLU fused; the output keeps
+    its NCHW shape and values, in channels-last storage.  A config selects it with dict(type='FPN_LSS', ..., conv_impl='hip')."""
+
     def __init__(self, in_channels, out_channels, scale_factor=4, input_feature_index=(0, 2), norm_cfg=None,
-                 extra_upsample=2, lateral=None, use_input_conv=False):
+                 extra_upsample=2, lateral=None, use_input_conv=False, conv_impl='torch'):
         super().__init__()
         if lateral is not None or use_input_conv:
             raise NotImplementedError('lateral / use_input_conv are not used by the PreWorld configs')
@@ -505,18 +587,39 @@ class FPN_LSS(nn.Module):
                 nn.Upsample(scale_factor=extra_upsample, mode='bilinear', align_corners=True),
                 nn.Conv2d(out_channels * cf, out_channels, 3, padding=1, bias=False), nn.BatchNorm2d(out_channels),
                 nn.ReLU(inplace=True), nn.Conv2d(out_channels, out_channels, 1, padding=0))
+        self.conv_impl = self.check_conv_impl(conv_impl)
+
+    def _own_convs(self):
+        convs = [('conv.0', self.conv[0]), ('conv.3', self.conv[3])]
+        if self.extra_upsample:
+            convs += [('up2.1', self.up2[1]), ('up2.4', self.up2[4])]
+        return convs
+
+    def _forward_hip(self, x2, x1):
+        x = _channels_last(torch.cat([_channels_last(x2), self.up(_channels_last(x1))], dim=1))      # both channels-last: so is the concat
+        x = self._conv(x, 'conv.0', self.conv[0], self.conv[1], relu=True)
+        x = self._conv(x, 'conv.3', self.conv[3], self.conv[4], relu=True)
+        if self.extra_upsample:
+            x = _channels_last(self.up2[0](x))
+            x = self._conv(x, 'up2.1', self.up2[1], self.up2[2], relu=True)
+            x = self._conv(x, 'up2.4', self.up2[4])
+        return x
 
     def forward(self, feats):
         x2, x1 = feats[self.input_feature_index[0]], feats[self.input_feature_index[1]]
+        if self._fused(x2, x1):
+            return self._forward_hip(x2, x1)
         x = self.conv(torch.cat([x2, self.up(x1)], dim=1))
         return self.up2(x) if self.extra_upsample else x
 
 
 # ----------------------------------------------------------------------------------------------- DepthNet
-class BasicBlock2d(nn.Module):
-    """mmdet.models.backbones.resnet.BasicBlock (2.24, third-party): 3x3 conv-BN-ReLU, 3x3 conv-BN, + downsample(x), ReLU."""
+class BasicBlock2d(_FusedConvs, nn.Module):
+    """mmdet.models.backbones.resnet.BasicBlock (2.24, third-party): 3x3 conv-BN-ReLU, 3x3 conv-BN, + downsample(x), ReLU.
+    conv_impl='hip' (_FusedConvs): three ops.conv2d calls -- conv1 with bn1 and ReLU, the downsample convolution if there is one, conv2
+    with bn2, the residual addition and ReLU.  A strided or grouped layer is refused where the block is built."""
 
-    def __init__(self, inplanes, planes, stride=1, downsample=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=None, conv_impl='torch'):
         super().__init__()
         self.conv1 = nn.Conv2d(inplanes, planes, 3, stride=stride, padding=1, bias=False)
         self.bn1 = nn.BatchNorm2d(planes)
@@ -524,38 +627,71 @@ class BasicBlock2d(nn.Module):
         self.bn2 = nn.BatchNorm2d(planes)
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
+        self.conv_impl = self.check_conv_impl(conv_impl)
+
+    def _own_convs(self):
+        return [('conv1', self.conv1), ('conv2', self.conv2)] + ([] if self.downsample is None else [('downsample', self.downsample)])
+
+    def _forward_hip(self, x):
+        x = _channels_last(x)
+        out = self._conv(x, 'conv1', self.conv1, self.bn1, relu=True)
+        identity = x if self.downsample is None else self._conv(x, 'downsample', self.downsample)
+        return self._conv(out, 'conv2', self.conv2, self.bn2, relu=True, residual=identity)
 
     def forward(self, x):
+        if self._fused(x):
+            return self._forward_hip(x)
         out = self.bn2(self.conv2(self.relu(self.bn1(self.conv1(x)))))
         return self.relu(out + (x if self.downsample is None else self.downsample(x)))
 
 
-class _ASPPModule(nn.Module):
-    def __init__(self, inplanes, planes, kernel_size, padding, dilation):
+class _ASPPModule(_FusedConvs, nn.Module):
+    def __init__(self, inplanes, planes, kernel_size, padding, dilation, conv_impl='torch'):
         super().__init__()
         self.atrous_conv = nn.Conv2d(inplanes, planes, kernel_size, stride=1, padding=padding, dilation=dilation, bias=False)
         self.bn = nn.BatchNorm2d(planes)
         self.relu = nn.ReLU()
+        self.conv_impl = self.check_conv_impl(conv_impl)
+
+    def _own_convs(self):
+        return [('atrous_conv', self.atrous_conv)]
 
     def forward(self, x):
+        if self._fused(x):
+            return self._conv(_channels_last(x), 'atrous_conv', self.atrous_conv, self.bn, relu=True)
         return self.relu(self.bn(self.atrous_conv(x)))
 
 
-class ASPP(nn.Module):
-    def __init__(self, inplanes, mid_channels=256):
+class ASPP(_FusedConvs, nn.Module):
+    """view_transformer.py:323-420.  conv_impl='hip' (_FusedConvs): the four branches and conv1 + bn1 + ReLU run ops.conv2d; the pooled
+    branch, its upsample and the concat stay on torch; the Dropout is an identity in eval mode, the only mode the fused path runs in."""
+
+    def __init__(self, inplanes, mid_channels=256, conv_impl='torch'):
         super().__init__()
-        self.aspp1 = _ASPPModule(inplanes, mid_channels, 1, 0, 1)
-        self.aspp2 = _ASPPModule(inplanes, mid_channels, 3, 6, 6)
-        self.aspp3 = _ASPPModule(inplanes, mid_channels, 3, 12, 12)
-        self.aspp4 = _ASPPModule(inplanes, mid_channels, 3, 18, 18)
+        self.aspp1 = _ASPPModule(inplanes, mid_channels, 1, 0, 1, conv_impl)
+        self.aspp2 = _ASPPModule(inplanes, mid_channels, 3, 6, 6, conv_impl)
+        self.aspp3 = _ASPPModule(inplanes, mid_channels, 3, 12, 12, conv_impl)
+        self.aspp4 = _ASPPModule(inplanes, mid_channels, 3, 18, 18, conv_impl)
         self.global_avg_pool = nn.Sequential(nn.AdaptiveAvgPool2d((1, 1)), nn.Conv2d(inplanes, mid_channels, 1, bias=False),
                                              nn.BatchNorm2d(mid_channels), nn.ReLU())
         self.conv1 = nn.Conv2d(int(mid_channels * 5), inplanes, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(inplanes)
         self.relu = nn.ReLU()
         self.dropout = nn.Dropout(0.5)
+        self.conv_impl = self.check_conv_impl(conv_impl)
+
+    def _own_convs(self):
+        return [('conv1', self.conv1)]
+
+    def _forward_hip(self, x):
+        x = _channels_last(x)
+        x5 = F.interpolate(self.global_avg_pool(x), size=x.shape[2:], mode='bilinear', align_corners=True)
+        x = torch.cat((self.aspp1(x), self.aspp2(x), self.aspp3(x), self.aspp4(x), _channels_last(x5)), dim=1)
+        return self._conv(_channels_last(x), 'conv1', self.conv1, self.bn1, relu=True)
 
     def forward(self, x):
+        if self._fused(x):
+            return self._forward_hip(x)
         x5 = F.interpolate(self.global_avg_pool(x), size=x.shape[2:], mode='bilinear', align_corners=True)
         x = torch.cat((self.aspp1(x), self.aspp2(x), self.aspp3(x), self.aspp4(x), x5), dim=1)
         return self.dropout(self.relu(self.bn1(self.conv1(x))))
@@ -586,13 +722,17 @@ class SELayer(nn.Module):
         return x * self.gate(self.conv_expand(self.act1(self.conv_reduce(x_se))))
 
 
-class DepthNet(nn.Module):
+class DepthNet(_FusedConvs, nn.Module):
     """view_transformer.py:471-638 with use_dcn=False (the PreWorld configs).  With `stereo_metas` holding a previous
     stereo feature the cost volume comes from ops.stereo_cost_volume (HIP, one kernel instead of the reference's 32
-    grid_sample rounds); without one it is zeros, as in the reference (:621-628)."""
+    grid_sample rounds); without one it is zeros, as in the reference (:621-628).
+    conv_impl='hip' (_FusedConvs; depthnet_cfg=dict(..., conv_impl='hip') in a config): reduce_conv, context_conv, the BasicBlocks, the
+    ASPP and the last depth_conv layer run ops.conv2d on channels-last maps; the BatchNorm1d, the Mlps, the SE gates and their
+    (B, C, 1, 1) convolutions, the concats and cost_volumn_net (stride 2) stay on torch.  The output keeps its NCHW shape and values,
+    in channels-last storage."""
 
     def __init__(self, in_channels, mid_channels, context_channels, depth_channels, use_dcn=True, use_aspp=True,
-                 with_cp=False, stereo=False, bias=0.0, aspp_mid_channels=-1, D=100):
+                 with_cp=False, stereo=False, bias=0.0, aspp_mid_channels=-1, D=100, conv_impl='torch'):
         super().__init__()
         if use_dcn:
             raise NotImplementedError('use_dcn=True (mmcv deformable conv) is not used by the PreWorld configs')
@@ -614,13 +754,33 @@ class DepthNet(nn.Module):
                 net += [nn.Conv2d(depth_channels, depth_channels, 3, stride=2, padding=1), nn.BatchNorm2d(depth_channels)]
             self.cost_volumn_net = nn.Sequential(*net)
             self.bias = bias
-        layers = [BasicBlock2d(cin, mid_channels, downsample=downsample), BasicBlock2d(mid_channels, mid_channels),
-                  BasicBlock2d(mid_channels, mid_channels)]
+        if conv_impl not in CONV_IMPLS:
+            raise ValueError('conv_impl must be one of %s, got %r' % (CONV_IMPLS, conv_impl))
+        layers = [BasicBlock2d(cin, mid_channels, downsample=downsample, conv_impl=conv_impl),
+                  BasicBlock2d(mid_channels, mid_channels, conv_impl=conv_impl), BasicBlock2d(mid_channels, mid_channels, conv_impl=conv_impl)]
         if use_aspp:
-            layers.append(ASPP(mid_channels, mid_channels if aspp_mid_channels < 0 else aspp_mid_channels))
+            layers.append(ASPP(mid_channels, mid_channels if aspp_mid_channels < 0 else aspp_mid_channels, conv_impl))
         layers.append(nn.Conv2d(mid_channels, depth_channels, 1))
         self.depth_conv = nn.Sequential(*layers)
         self.depth_channels = depth_channels
+        self.conv_impl = self.check_conv_impl(conv_impl)
+
+    def _own_convs(self):
+        return [('reduce_conv.0', self.reduce_conv[0]), ('context_conv', self.context_conv),
+                ('depth_conv.%d' % (len(self.depth_conv) - 1), self.depth_conv[-1])]
+
+    def _forward_hip(self, x, mlp_input, stereo_metas):
+        x = self._conv(_channels_last(x), 'reduce_conv.0', self.reduce_conv[0], self.reduce_conv[1], relu=True)
+        context = self.context_se(x, self.context_mlp(mlp_input)[..., None, None])
+        context = self._conv(_channels_last(context), 'context_conv', self.context_conv)
+        depth = self.depth_se(x, self.depth_mlp(mlp_input)[..., None, None])
+        if stereo_metas is not None:
+            depth = torch.cat([_channels_last(depth), _channels_last(self.cost_volumn_net(self._cost_volume(x, stereo_metas)))], dim=1)
+        depth = _channels_last(depth)
+        for layer in self.depth_conv[:-1]:
+            depth = layer(depth)                          # BasicBlock2d / ASPP: their own fused path
+        depth = self._conv(depth, 'depth_conv.%d' % (len(self.depth_conv) - 1), self.depth_conv[-1])
+        return torch.cat([depth, context], dim=1)
 
     def calculate_cost_volumn(self, metas):
         from . import ops
@@ -628,20 +788,23 @@ class DepthNet(nn.Module):
         return ops.stereo_cost_volume(prev, curr, metas['frustum'], metas['k2s_sensor'], metas['intrins'],
                                       metas['post_rots'], metas['post_trans'], bias=self.bias)
 
+    def _cost_volume(self, x, stereo_metas):
+        if stereo_metas['cv_feat_list'][0] is None:
+            BN, _, H, W = x.shape
+            s = float(stereo_metas['downsample']) / stereo_metas['cv_downsample']
+            return torch.zeros((BN, self.depth_channels, int(H * s), int(W * s))).to(x)
+        with torch.no_grad():
+            return self.calculate_cost_volumn(stereo_metas)
+
     def forward(self, x, mlp_input, stereo_metas=None):
         mlp_input = self.bn(mlp_input.reshape(-1, mlp_input.shape[-1]))
+        if self._fused(x, mlp_input):
+            return self._forward_hip(x, mlp_input, stereo_metas)
         x = self.reduce_conv(x)
         context = self.context_conv(self.context_se(x, self.context_mlp(mlp_input)[..., None, None]))
         depth = self.depth_se(x, self.depth_mlp(mlp_input)[..., None, None])
         if stereo_metas is not None:
-            if stereo_metas['cv_feat_list'][0] is None:
-                BN, _, H, W = x.shape
-                s = float(stereo_metas['downsample']) / stereo_metas['cv_downsample']
-                cv = torch.zeros((BN, self.depth_channels, int(H * s), int(W * s))).to(x)
-            else:
-                with torch.no_grad():
-                    cv = self.calculate_cost_volumn(stereo_metas)
-            depth = torch.cat([depth, self.cost_volumn_net(cv)], dim=1)
+            depth = torch.cat([depth, self.cost_volumn_net(self._cost_volume(x, stereo_metas))], dim=1)
         return torch.cat([self.depth_conv(depth), context], dim=1)
 
 
@@ -679,8 +842,12 @@ class ImageBranch(nn.Module):
     intrin, post_rot, post_tran, bda) -- exactly what modules.PreWorld4DTraj.simple_test_from_lift consumes (key first)."""
 
     def __init__(self, backbone_cfg, neck_cfg, depthnet_cfg, grid_depth, input_size, downsample=16, out_channels=32,
-                 in_channels=512):
+                 in_channels=512, conv_impl=None):
         super().__init__()
+        if conv_impl is not None:                         # over what the two configs say; None leaves them as they are
+            if conv_impl not in CONV_IMPLS:
+                raise ValueError('conv_impl must be one of %s, got %r' % (CONV_IMPLS, conv_impl))
+            neck_cfg, depthnet_cfg = dict(neck_cfg, conv_impl=conv_impl), dict(depthnet_cfg, conv_impl=conv_impl)
         self.img_backbone = SwinTransformer(**backbone_cfg)
         self.img_neck = FPN_LSS(**neck_cfg)
         self.img_view_transformer = nn.Module()
@@ -688,6 +855,21 @@ class ImageBranch(nn.Module):
         self.img_view_transformer.depth_net = DepthNet(in_channels, in_channels, out_channels, self.D, **depthnet_cfg)
         self.out_channels, self.downsample = out_channels, downsample
         self.register_buffer('cv_frustum', create_frustum(grid_depth, input_size, 4), persistent=False)
+
+    @property
+    def conv_impl(self):
+        """'torch' or 'hip' (FPN_LSS and DepthNet, see _FusedConvs), or 'mixed' if the two were configured differently"""
+        a, b = self.img_neck.conv_impl, self.img_view_transformer.depth_net.conv_impl
+        return a if a == b else 'mixed'
+
+    def set_conv_impl(self, conv_impl):
+        """switch the neck and the DepthNet between 'torch' and 'hip' (the fused convolutions); a layer the kernel does not take raises
+        before either is switched"""
+        parts = (self.img_neck, self.img_view_transformer.depth_net)
+        for m in parts:
+            m.check_conv_impl(conv_impl)
+        for m in parts:
+            m.set_conv_impl(conv_impl)
 
     def image_encoder(self, img):
         B, N, C, H, W = img.shape

@@ -2463,3 +2463,113 @@ class SwinLinear(torch.autograd.Function):
             dx = dres
         dresidual = g.view(shape) if role == 'res' and need[5] else None
         return (dx, dw, db, dg if need[3] else None, dbeta if need[4] else None, dresidual, None, None, None, None)
+
+
+# ------------------------------------------------------------------- FPN_LSS / DepthNet convolutions (include/preworld_hip_conv2d.h)
+CONV2D_MIN_DIM, CONV2D_MAX_DIM = _lib.PW_CONV2D['PW_CONV2D_MIN_DIM'], _lib.PW_CONV2D['PW_CONV2D_MAX_DIM']
+
+
+class Conv2dPacked:
+    """the packed operand of one convolution for pw_conv2d: `buf` (uint8, pw_conv2d_packed_bytes: the split-fp16 weight planes and the
+    folded BatchNorm / bias), Cin, Cout and ksize"""
+    __slots__ = ('buf', 'Cin', 'Cout', 'ksize')
+
+    def __init__(self, buf, Cin, Cout, ksize):
+        self.buf, self.Cin, self.Cout, self.ksize = buf, Cin, Cout, ksize
+
+
+def _pair(v):
+    return (v, v) if isinstance(v, int) else tuple(v)
+
+
+def conv2d_supported(Cin, Cout, ksize, stride=1, dilation=1, padding=0, groups=1):
+    """None if pw_conv2d takes an nn.Conv2d with these arguments (ints or pairs, as nn.Conv2d stores them), else the reason it does
+    not: square 1x1 or 3x3, stride 1, groups 1, padding dilation (ksize - 1) / 2, channels multiples of 4 in 4 .. 4096"""
+    ks, st, dl, pd = _pair(ksize), _pair(stride), _pair(dilation), _pair(padding)
+    if ks not in ((1, 1), (3, 3)):
+        return 'kernel_size %s (supported: 1 and 3)' % (ks,)
+    if st != (1, 1):
+        return 'stride %s (supported: 1)' % (st,)
+    if groups != 1:
+        return 'groups %d (supported: 1)' % groups
+    if dl[0] != dl[1] or dl[0] < 1:
+        return 'dilation %s (supported: one value >= 1 for both axes)' % (dl,)
+    want = dl[0] * (ks[0] - 1) // 2
+    if pd != (want, want):
+        return "padding %s (supported: dilation (kernel_size - 1) / 2 = %d, the 'same' size)" % (pd, want)
+    for what, v in (('in_channels', Cin), ('out_channels', Cout)):
+        if v % 4 or not CONV2D_MIN_DIM <= v <= CONV2D_MAX_DIM:
+            return '%s %d (supported: multiples of 4 in %d .. %d)' % (what, v, CONV2D_MIN_DIM, CONV2D_MAX_DIM)
+    return None
+
+
+def conv2d_pack(conv, bn=None):
+    """Pack an nn.Conv2d (float32, on the device) and the eval-mode nn.BatchNorm2d behind it, if any, for conv2d: the weight rows as
+    split-fp16 planes under per-row powers of two, and scale = gamma / sqrt(var + eps), shift = beta + (bias - mean) scale (without a
+    BatchNorm: 1 and the bias), computed on the device from the raw parameters and running statistics.  One launch, no
+    synchronisation.  The dilation is an argument of conv2d, not of the packed operand."""
+    fn = 'conv2d_pack'
+    why = conv2d_supported(conv.in_channels, conv.out_channels, conv.kernel_size, conv.stride, conv.dilation, conv.padding, conv.groups)
+    if why is not None:
+        raise _lib.PreworldHipError('%s: not supported: %s' % (fn, why))
+    if getattr(conv, 'padding_mode', 'zeros') != 'zeros':
+        raise _lib.PreworldHipError('%s: not supported: padding_mode %r' % (fn, conv.padding_mode))
+    Cin, Cout, ks = conv.in_channels, conv.out_channels, conv.kernel_size[0]
+    named = [('weight', conv.weight, (Cout, Cin, ks, ks)), ('bias', conv.bias, (Cout,))]
+    if bn is not None:
+        if bn.num_features != Cout or bn.running_mean is None or bn.running_var is None:
+            raise _lib.PreworldHipError('%s: bn must be a BatchNorm2d over %d channels with running statistics' % (fn, Cout))
+        named += [('bn.weight', bn.weight, (Cout,)), ('bn.bias', bn.bias, (Cout,)), ('bn.running_mean', bn.running_mean, (Cout,)),
+                  ('bn.running_var', bn.running_var, (Cout,))]
+    for name, t, shape in named:
+        if t is not None and (tuple(t.shape) != shape or t.dtype != _f32 or not t.is_contiguous()):
+            raise _lib.PreworldHipError('%s: %s must be a contiguous float32 %s tensor, got %s %s' % (fn, name, shape, t.dtype, tuple(t.shape)))
+    if bn is not None and (bn.weight is None or bn.bias is None):
+        raise _lib.PreworldHipError('%s: not supported: a BatchNorm2d without affine parameters' % fn)
+    nbytes = _lib.call_size('pw_conv2d_packed_bytes', Cin, Cout, ks)
+    if not conv.weight.is_cuda:
+        raise _lib.PreworldHipError('%s: weight must be a CUDA(HIP) tensor' % fn)
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=conv.weight.device)
+    d = lambda t: None if t is None else t.detach()
+    stats = (None,) * 4 if bn is None else (d(bn.weight), d(bn.bias), d(bn.running_mean), d(bn.running_var))
+    _lib.call('pw_conv2d_pack', d(conv.weight), d(conv.bias), *stats, float(bn.eps) if bn is not None else 0.0, buf, Cin, Cout, ks, _lib.STREAM)
+    return Conv2dPacked(buf, Cin, Cout, ks)
+
+
+def _conv2d_map(fn, name, t, shape):
+    """t: a float32 NCHW-shaped tensor of this shape in torch.channels_last storage, i.e. (B, H, W, C) contiguous in memory"""
+    if t.dim() != 4 or tuple(t.shape) != tuple(shape) or t.dtype != _f32:
+        raise _lib.PreworldHipError('%s: %s must be a float32 %s tensor, got %s %s' % (fn, name, tuple(shape), t.dtype, tuple(t.shape)))
+    if not t.permute(0, 2, 3, 1).is_contiguous():
+        raise _lib.PreworldHipError('%s: %s must be in torch.channels_last storage ((B, H, W, C) contiguous), got strides %s; '
+                                    'convert it with .contiguous(memory_format=torch.channels_last)' % (fn, name, tuple(t.stride())))
+
+
+def conv2d(x, packed, *, dilation=1, relu=False, residual=None):
+    """out = epi(scale . conv(x) + shift) in one implicit GEMM (include/preworld_hip_conv2d.h): the stride-1 'same' convolution that
+    conv2d_pack packed, at this dilation, with its BatchNorm and bias folded; relu=True applies ReLU; residual (the output's shape) is
+    added before the ReLU (needs relu=True: BasicBlock's tail).  x (B, Cin, H, W), residual and the result (B, Cout, H, W) are float32
+    NCHW-shaped tensors in torch.channels_last storage; a tensor in another layout is refused, never copied.  Two launches: the
+    partial maxima of |x| (1 KB of workspace), then the GEMM.  Forward only, no synchronisation."""
+    fn = 'conv2d'
+    if not isinstance(packed, Conv2dPacked):
+        raise _lib.PreworldHipError('%s: packed must come from conv2d_pack' % fn)
+    if residual is not None and not relu:
+        raise _lib.PreworldHipError('%s: residual needs relu=True (out = max(y + residual, 0))' % fn)
+    if not isinstance(dilation, int) or dilation < 1:
+        raise _lib.PreworldHipError('%s: dilation must be a positive int, got %r' % (fn, dilation))
+    if x.dim() != 4 or x.numel() == 0:
+        raise _lib.PreworldHipError('%s: x must be (B, %d, H, W) and not empty, got %s' % (fn, packed.Cin, tuple(x.shape)))
+    B, _, H, W = x.shape
+    _conv2d_map(fn, 'x', x, (B, packed.Cin, H, W))
+    if residual is not None:
+        _conv2d_map(fn, 'residual', residual, (B, packed.Cout, H, W))
+    if not x.is_cuda or (residual is not None and not residual.is_cuda) or packed.buf.device != x.device:
+        raise _lib.PreworldHipError('%s: x%s must be a CUDA(HIP) tensor on the device of the packed operand' % (fn, '' if residual is None else ', residual'))
+    out = torch.empty((B, H, W, packed.Cout), device=x.device, dtype=_f32).permute(0, 3, 1, 2)
+    epi = 'PW_CONV2D_EPI_RESIDUAL_RELU' if residual is not None else ('PW_CONV2D_EPI_RELU' if relu else 'PW_CONV2D_EPI_NONE')
+    nbytes = _lib.call_size('pw_conv2d_workspace_bytes', B, H, W)
+    wsp = torch.empty(nbytes // 4, device=x.device, dtype=_f32)
+    _lib.call('pw_conv2d', _lib.strided(x), packed.buf, None if residual is None else _lib.strided(residual), _lib.strided(out), wsp, nbytes,
+              B, H, W, packed.Cin, packed.Cout, packed.ksize, dilation, _lib.PW_CONV2D[epi], _lib.STREAM)
+    return out

@@ -56,11 +56,12 @@ class ImagePath:
     def step(self):
         return self.cap.run(self._f32(self.image_side()), self.ego)
 
-    def run(self, amp='none', attn='torch', steps=10, linear='torch'):
+    def run(self, amp='none', attn='torch', steps=10, linear='torch', conv='torch'):
         self.amp = amp
         self.branch.img_backbone.set_linear_impl('torch')        # 'hip' Linears need a fused attention: switch in an order that holds
         self.branch.img_backbone.set_attn_impl(attn)
         self.branch.img_backbone.set_linear_impl(linear)
+        self.branch.set_conv_impl(conv)                           # FPN_LSS and DepthNet: torch convolutions or the fused HIP implicit GEMM
         for _ in range(2):
             self.step()
         torch.cuda.synchronize()
@@ -77,7 +78,7 @@ class ImagePath:
         return {'metric': 'image -> occupancy samples/s (C3, 1 GPU, serial)', 'value': round(1.0 / t_all, 2),
                 'ms_per_sample': round(t_all * 1e3, 2), 'image_branch_ms': round(t_img * 1e3, 2),
                 'voxel_path_ms': round((t_all - t_img) * 1e3, 2), 'image_branch_dtype': 'f32' if amp == 'none' else 'bf16 autocast',
-                'window_attention': attn, 'block_linears': linear, 'image_branch_params': self.n_par,
+                'window_attention': attn, 'block_linears': linear, 'neck_depthnet_convs': conv, 'image_branch_params': self.n_par,
                 'images': '6 cams x (key + adjacent full backbone, extra reference stage 0), 3x512x1408',
                 'data': 'synthetic, random weights'}
 
@@ -89,8 +90,10 @@ def main():
     ap.add_argument('--attn', choices=['torch', 'hip'], default='torch', help="the Swin blocks' window attention: torch ops or the fused HIP kernel")
     ap.add_argument('--linear', choices=['torch', 'hip'], default='torch',
                     help="the Swin blocks' Linears, LayerNorms, GELU and residuals: torch ops or the fused HIP GEMM (needs --attn hip)")
+    ap.add_argument('--conv', choices=['torch', 'hip'], default='torch',
+                    help="the stride-1 convolutions of FPN_LSS and DepthNet: torch ops or the fused HIP implicit GEMM (float32, not with --amp bf16)")
     a = ap.parse_args()
-    print(json.dumps(ImagePath().run(a.amp, a.attn, a.steps, a.linear)))
+    print(json.dumps(ImagePath().run(a.amp, a.attn, a.steps, a.linear, a.conv)))
 
 
 if __name__ == '__main__':
