@@ -17,8 +17,21 @@ THE BOUND.  Per case 4 x FLOORS[case], relative to max |out64|, no element exclu
 max |out64| of the EXISTING torch modules on the CPU in float32 -- F.conv2d, F.batch_norm in eval mode, the addition and ReLU --
 measured by tests/test_conv2d_cpu.py, which asserts that the torch path stays under each entry (rounded up to two digits) and
 reaches at least half of it: never taken from the kernel.  The factor covers a different summation order and the matrix-core
-products, as for the Linears (tests/_swin_linear_ref64.py)."""
+products, as for the Linears (tests/_swin_linear_ref64.py).
+
+THE UNIT.  That figure divides by the tensor's largest element, so an error in a dim image, a small channel or a corner pixel
+vanishes in it (tests/test_conv2d_cpu.py::test_the_unit_sees_what_the_tensor_maximum_hides).  Every case is therefore ALSO scored per
+element, as tests/_infer_ref64.py scores the voxel side:
+    q = |out - out64| / (2^-24 n),      n = conv2d(|x|, |w|) |scale| + |shift| + |residual|
+with scale = gamma / sqrt(var + eps) and shift = beta + (bias - mean) scale, the folded BatchNorm and bias in float64 (fold64; a
+ReLU passes n through unchanged; an element with n == 0 must be reproduced exactly).  The bound is max q <= 2 Q32[case] + 1 +
+FORMAT_TERM.get(case, 0): Q32 is the worst q of the same float32 torch path on one CPU thread, rounded up to two digits and asserted
+by tests/test_conv2d_cpu.py like FLOORS; FORMAT_TERM holds a-priori terms only (profiles/image_gemm_units.md).  Four cases aim at
+the exponents -- the kernel takes ONE power of two for all of x and one per weight row: dim_image (the second image x 2^-14, no
+BatchNorm or bias, so its outputs are judged at their own size), dim_corner (the rows h < 6 x 2^-14 under dilation 6), w_rows_span
+(weight row n x 2^((n % 25) - 12), Cout = 88: the n tail) and bn_scale_span (gamma and beta of channel c x 2^-(c % 11))."""
 import collections
+import contextlib
 import functools
 import math
 
@@ -53,9 +66,16 @@ CASES = collections.OrderedDict([
     ('big_deep_small_tile', _c(1, 9, 11, 144, 88, 3, 1, 'residual_relu', 15)),          # 64 x 64 blocked sum with row, column and Cin tails
     ('big_1x1', _c(2, 32, 85, 144, 272, 1, 1, 'none', 16, bn=False, bias=True)),     # 128 x 128 tile
     ('big_3x3', _c(2, 32, 85, 144, 272, 3, 1, 'relu', 17)),                          # 128 x 64 tile, blocked sum
+    # the exponents (see THE UNIT): what one power of two for all of x, and one per weight row, do to the small values
+    ('dim_image', _c(2, 7, 9, 64, 64, 3, 1, 'none', 18, bn=False, special='dim_image')),      # the second image x 2^-14, no shift
+    ('dim_corner', _c(1, 20, 15, 32, 16, 3, 6, 'relu', 19, special='dim_corner')),   # the rows h < 6 x 2^-14 under dilation 6
+    ('w_rows_span', _c(1, 9, 11, 32, 88, 3, 1, 'none', 20, bn=False, special='w_rows_span')),      # weight row n x 2^((n % 25) - 12), n tail
+    ('bn_scale_span', _c(1, 9, 11, 32, 32, 3, 1, 'relu', 21, special='bn_scale_span')),      # folded scale and shift of channel c x 2^-(c % 11)
 ])
 EPS = 1e-5
 OUTLIER_CHANNEL = 5
+DIM = 2.0 ** -14
+U = 2.0 ** -24
 
 # max |out_torch - out64| / max |out64| of the torch path on the CPU in float32 (see the module docstring), rounded up to two digits
 FLOORS = {
@@ -77,7 +97,39 @@ FLOORS = {
     'big_deep_small_tile': 3.7e-07,          # measured 3.654e-07
     'big_1x1': 4.2e-07,                      # measured 4.132e-07
     'big_3x3': 3.1e-07,                      # measured 3.044e-07
+    'dim_image': 2.9e-07,                    # measured 2.852e-07
+    'dim_corner': 6.8e-07,                   # measured 6.720e-07
+    'w_rows_span': 4.0e-07,                  # measured 3.972e-07
+    'bn_scale_span': 2.8e-07,                # measured 2.759e-07
 }
+
+# worst q of the same torch path in the units of THE UNIT (2^-24 n), rounded up to two digits
+Q32 = {
+    'toy_3x3': 1.5,                          # measured 1.442, mean 0.139
+    'far_taps': 1.5,                         # measured 1.426, mean 0.152
+    'dil6_edges': 2.4,                       # measured 2.333, mean 0.162
+    'dil12_edges': 3,                        # measured 2.991, mean 0.173
+    'image_seam': 1.8,                       # measured 1.744, mean 0.257
+    'cin_tail': 2.4,                         # measured 2.343, mean 0.171
+    'cin_600': 0.58,                         # measured 0.5735, mean 0.037
+    'cout_88_1x1': 3.7,                      # measured 3.655, mean 0.334
+    'neck_deep': 0.36,                       # measured 0.3541, mean 0.026
+    'res_relu': 1.5,                         # measured 1.448, mean 0.073
+    'bn_fold': 4.8,                          # measured 4.79, mean 0.308
+    'outlier_channel': 16,                   # measured 15.11, mean 0.988
+    'range_2m12': 1.3,                       # measured 1.296, mean 0.094
+    'range_2p8': 1.3,                        # measured 1.296, mean 0.094
+    'zero_image': 1.8,                       # measured 1.764, mean 0.409
+    'big_deep_small_tile': 1.6,              # measured 1.546, mean 0.090
+    'big_1x1': 5.5,                          # measured 5.41, mean 0.330
+    'big_3x3': 1.1,                          # measured 1.038, mean 0.065
+    'dim_image': 1.3,                        # measured 1.265, mean 0.187
+    'dim_corner': 4,                         # measured 3.995, mean 0.200
+    'w_rows_span': 3.5,                      # measured 3.467, mean 0.332
+    'bn_scale_span': 3.6,                    # measured 3.533, mean 0.169
+}
+# a-priori terms of the format, in units of 2^-24 n (profiles/image_gemm_units.md); never fitted to a measured q
+FORMAT_TERM = {}
 
 # the two modules at real width (build_neck / build_depthnet below): the torch module in float32 on the CPU against the same module
 # in float64, rounded up to two digits
@@ -128,6 +180,15 @@ def inputs(name):
         x[:, OUTLIER_CHANNEL] *= 2.0 ** 10
     if c.special == 'zero':
         x = torch.zeros_like(x)
+    if c.special == 'dim_image':
+        x[1] *= DIM
+    if c.special == 'dim_corner':
+        x[:, :, :c.dil] *= DIM
+    if c.special == 'w_rows_span':
+        w = w * torch.pow(2.0, (torch.arange(c.Cout) % 25 - 12).float()).view(-1, 1, 1, 1)
+    if c.special == 'bn_scale_span':                       # gamma and beta: the channel's whole output is scaled
+        f = torch.pow(2.0, -(torch.arange(c.Cout) % 11).float())
+        bn[0], bn[1] = bn[0] * f, bn[1] * f
     if c.x_scale != 1.0:                                   # x, residual and everything that enters the shift
         x, res, b = x * c.x_scale, res * c.x_scale, b * c.x_scale
         bn[1], bn[2] = bn[1] * c.x_scale, bn[2] * c.x_scale
@@ -167,6 +228,64 @@ def torch_path(name, dtype=torch.float32):
 
 def rel_err(out, ref):
     return float((out.double() - ref.double()).abs().max() / ref.double().abs().max())
+
+
+# ------------------------------------------------------------------------------------------------------- the unit, per element
+def fold64(name):
+    """(scale, shift) (Cout,) of the eval-mode BatchNorm and the bias behind a case's convolution, in float64:
+    y = conv(x, w) scale + shift"""
+    c, i = CASES[name], inputs(name)
+    bias = torch.zeros(c.Cout, dtype=torch.float64) if i['bias'] is None else i['bias'].double()
+    if i['bn'] is None:
+        return torch.ones(c.Cout, dtype=torch.float64), bias
+    g, beta, mean, var = (t.double() for t in i['bn'])
+    scale = g / torch.sqrt(var + EPS)
+    return scale, beta + (bias - mean) * scale
+
+
+@functools.lru_cache(maxsize=None)
+def normaliser(name):
+    """n = conv2d(|x|, |w|) |scale| + |shift| + |residual| in float64, (B, Cout, H, W); a ReLU passes it through unchanged.  Computed
+    once and shared (do not modify)"""
+    c, i = CASES[name], inputs(name)
+    scale, shift = fold64(name)
+    n = F.conv2d(i['x'].double().abs(), i['weight'].double().abs(), None, stride=1, padding=padding(c), dilation=c.dil)
+    n = n * scale.abs().view(1, -1, 1, 1) + shift.abs().view(1, -1, 1, 1)
+    return n if i['residual'] is None else n + i['residual'].double().abs()
+
+
+@contextlib.contextmanager
+def one_thread():
+    """a CPU measurement that gives the same figure on every machine: torch picks a GEMM's blocking, and so the order of its sums, by
+    the thread count"""
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(threads)
+
+
+def q_of(got, ref, n):
+    """per-element q = |got - ref| / (2^-24 n) in double; where n == 0 the element must be reproduced exactly (q = inf otherwise); a
+    NaN counts as inf"""
+    err = (got.double() - ref).abs()
+    err = torch.where(torch.isnan(err), torch.full_like(err, float('inf')), err)
+    return torch.where(n > 0, err / (U * n.clamp_min(1e-300)), torch.where(err > 0, torch.full_like(err, float('inf')), err))
+
+
+def bound(name):
+    return 2.0 * Q32[name] + 1.0 + FORMAT_TERM.get(name, 0.0)
+
+
+def check_units(name, out, say):
+    """a case's output in per-element units against bound(name); prints the figures before it asserts; returns (worst, mean) q"""
+    q = q_of(out.cpu(), reference(name), normaliser(name))
+    worst, mean = float(q.max()), float(q.mean())
+    print('%s: %s worst q %.3f, mean q %.3f, Q32 %.2f, bound %.2f, variant %s' % (name, say, worst, mean, Q32[name], bound(name),
+                                                                                 tile_variant(CASES[name])))
+    assert worst <= bound(name), (name, worst, bound(name))
+    return worst, mean
 
 
 # ------------------------------------------------------------------------------------------------------------ harness (project code)

@@ -5,19 +5,36 @@ bias, gamma, beta and residual as leaves.  Nothing here comes from the kernel or
 THE COTANGENT of a case is a seeded standard normal of the output's shape (the cot_* cases reshape it, see below).
 
 THE CASES are the float32 entries of _swin_linear_ref64.CASES -- already the smallest shapes that reach each tile, tail and
-deep-accumulation path -- and four that only a backward can get wrong:
+deep-accumulation path, its *_span cases included -- and six that only a backward can get wrong:
     long_m               role ln,       M = 20011, K = 16, N = 48   the split over M and the order of the partial sums
     cot_rows_span        role res,      96 x 256 x 256              cotangent row i scaled by 2^((i % 25) - 12): per-row exponents of
                                                                     the data gradient, per-column exponents of the weight gradient
     cot_outlier_column   role ln,       96 x 512 x 512              one output channel's cotangent 2^10 x the rest
     cot_zero_rows        role ln_gelu,  64 x 128 x 512              an all-zero cotangent row: exponent 0, an exact-zero dx row
+    x_rows_span_wgrad    role res,      96 x 256 x 256              x row i scaled by 2^((i % 25) - 12), a plain cotangent: every column
+                                                                    of x the weight gradient takes an exponent of spans 2^24
+    x_cols_span_wgrad    role res,      96 x 256 x 256              x column k scaled by 2^((k % 25) - 12): small columns of dweight
 
 THE BOUND.  Per case and per gradient (dx, dweight, dbias, dgamma, dbeta, dresidual):
     max |g - g64| / max |g64| <= 4 x BWD_FLOORS[case][grad]
 The floor is the same figure for the float32 backward of the EXISTING torch modules (F.layer_norm, F.linear, F.gelu, the addition)
 on the CPU, on one thread with deterministic algorithms (_swin_attn_bwd_ref64._repeatable); tests/test_swin_linear_bwd_cpu.py
 measures it and asserts that the torch path stays under each entry (rounded up to two digits) and reaches at least half of it.  No
-floor is taken from the kernel, no element is excluded, and dresidual must equal the cotangent exactly (its floor is None)."""
+floor is taken from the kernel, no element is excluded, and dresidual must equal the cotangent exactly (its floor is None).
+
+THE UNIT.  As in _swin_linear_ref64 (THE UNIT there) every gradient is ALSO scored per element, q = |g - g64| / (2^-24 n), with one
+normaliser per gradient: the float64 formula of the gradient with products of absolute values and sums only.  With g the cotangent,
+r = 1 / sqrt(var + eps), n_xhat = (|x| + |mean|) r, n_t = n_xhat |gamma| + |beta| and |g_pre| = |g| (role ln, res) or
+|g| |gelu'(y64)| (role ln_gelu):
+    dbias      sum_m |g_pre|                              dweight    |g_pre|^T n_t        (role res: |g|^T |x|)
+    dx (res)   |g| |W|                                    dresidual  exactly the cotangent, not scored
+    dt = g_pre W, the gradient of the LayerNorm's output:            n_dt = |g_pre| |W|
+    dbeta  = sum_m dt                                                n = sum_m n_dt
+    dgamma = sum_m dt xhat                                           n = sum_m n_dt n_xhat
+    dxhat  = dt gamma                                                n_dxhat = n_dt |gamma|
+    dx     = r (dxhat - mean_k dxhat - xhat mean_k(dxhat xhat))      n = r (n_dxhat + mean_k n_dxhat + n_xhat mean_k(n_dxhat n_xhat))
+The bound is max q <= 2 Q32[case][grad] + 1 + FORMAT_TERM: Q32 is the worst q of the same float32 torch backward, asserted like
+BWD_FLOORS.  An element with n == 0 (the dx row of an all-zero cotangent row) must be exactly zero."""
 import collections
 import functools
 import math
@@ -37,6 +54,8 @@ NEW_CASES = collections.OrderedDict([
     ('cot_rows_span', R._c('res', 96, 256, 256, seed=42, special='cot_rows_span')),
     ('cot_outlier_column', R._c('ln', 96, 512, 512, seed=43, special='cot_outlier_column')),
     ('cot_zero_rows', R._c('ln_gelu', 64, 128, 512, seed=44, special='cot_zero_rows')),
+    ('x_rows_span_wgrad', R._c('res', 96, 256, 256, seed=45, special='x_rows_span')),
+    ('x_cols_span_wgrad', R._c('res', 96, 256, 256, seed=46, special='x_cols_span')),
 ])
 CASES = collections.OrderedDict([(k, c) for k, c in R.CASES.items() if c.dtype == 'f32'])
 CASES.update(NEW_CASES)
@@ -72,7 +91,48 @@ BWD_FLOORS = {
     'cot_rows_span':             dict(dx=4.6e-07, dweight=4.9e-07, dbias=1.4e-07),      # measured 4.523e-07, 4.815e-07, 1.320e-07
     'cot_outlier_column':        dict(dx=1.3e-06, dweight=2.0e-07, dbias=3.3e-07, dgamma=2.6e-07, dbeta=1.9e-06),      # measured 1.277e-06, 1.939e-07, 3.296e-07, 2.504e-07, 1.823e-06
     'cot_zero_rows':             dict(dx=4.3e-07, dweight=3.4e-07, dbias=1.7e-07, dgamma=3.7e-07, dbeta=2.2e-07),      # measured 4.298e-07, 3.369e-07, 1.681e-07, 3.608e-07, 2.109e-07
+    'w_rows_span':               dict(dx=5.0e-07, dweight=3.4e-07, dbias=1.2e-07),      # measured 4.986e-07, 3.305e-07, 1.120e-07
+    'w_rows_span_ln_gelu':       dict(dx=5.2e-05, dweight=3.0e-05, dbias=2.1e-05, dgamma=2.4e-05, dbeta=1.2e-05),      # measured 5.189e-05, 2.994e-05, 2.037e-05, 2.310e-05, 1.184e-05
+    'x_and_w_span':              dict(dx=4.4e-07, dweight=2.9e-07),      # measured 4.305e-07, 2.813e-07
+    'x_rows_span_wgrad':         dict(dx=5.3e-07, dweight=3.5e-07, dbias=1.5e-07),      # measured 5.248e-07, 3.433e-07, 1.408e-07
+    'x_cols_span_wgrad':         dict(dx=4.5e-07, dweight=2.9e-07, dbias=1.1e-07),      # measured 4.479e-07, 2.885e-07, 1.068e-07
 }
+
+# worst q of the same float32 backward in the units of THE UNIT (2^-24 n), rounded up to two digits, same order
+Q32 = {
+    'qkv_tile':                  dict(dx=1.7, dweight=4.1, dbias=0.48, dgamma=0.12, dbeta=0.17),      # measured 1.658, 4.012, 0.474, 0.1119, 0.1628
+    'm_tail':                    dict(dx=1.6, dweight=4.6, dbias=1.1, dgamma=0.15, dbeta=0.12),      # measured 1.515, 4.538, 1.069, 0.1406, 0.1143
+    'toy_narrow_qkv':            dict(dx=1.2, dweight=2.3, dbias=1.1, dgamma=0.16, dbeta=0.18),      # measured 1.164, 2.221, 1.031, 0.1552, 0.1739
+    'toy_narrow_proj':           dict(dx=4, dweight=1.9, dbias=0.65),      # measured 3.927, 1.849, 0.65
+    'toy_narrow_fc1':            dict(dx=1.4, dweight=2.3, dbias=1.2, dgamma=0.27, dbeta=0.28),      # measured 1.34, 2.3, 1.165, 0.2655, 0.2709
+    'toy_narrow_fc2':            dict(dx=2.3, dweight=3, dbias=0.55),      # measured 2.282, 2.914, 0.5489
+    'k_deep_res':                dict(dx=2.1, dweight=6.5, dbias=1.1),      # measured 2.002, 6.466, 1.087
+    'wide_n_gelu':               dict(dx=0.53, dweight=12, dbias=3.6, dgamma=0.12, dbeta=0.098),      # measured 0.524, 11.97, 3.521, 0.1133, 0.09751
+    'rows_span':                 dict(dx=3.7, dweight=9.1, dbias=0.67),      # measured 3.669, 9.015, 0.6609
+    'outlier_channel_res':       dict(dx=2.8, dweight=5, dbias=0.72),      # measured 2.715, 4.988, 0.7153
+    'outlier_channel_ln':        dict(dx=1.3, dweight=5.6, dbias=0.63, dgamma=0.25, dbeta=0.14),      # measured 1.251, 5.536, 0.6283, 0.245, 0.1343
+    'range_2m12':                dict(dx=3.7, dweight=3.9, dbias=0.65),      # measured 3.608, 3.855, 0.6453
+    'range_2p8':                 dict(dx=3.7, dweight=3.9, dbias=0.65),      # measured 3.608, 3.855, 0.6453
+    'degenerate_rows_ln':        dict(dx=1.7, dweight=1.7, dbias=0.7, dgamma=0.034, dbeta=0.21),      # measured 1.683, 1.607, 0.6903, 0.03306, 0.2043
+    'degenerate_rows_res':       dict(dx=4, dweight=3.6, dbias=0.67),      # measured 3.919, 3.507, 0.6671
+    'gelu_tails':                dict(dx=1.3, dweight=5.8, dbias=2.6, dgamma=0.22, dbeta=0.21),      # measured 1.295, 5.752, 2.542, 0.215, 0.2016
+    'no_ln_bias_zero':           dict(dx=3.4, dweight=3.4),      # measured 3.361, 3.374
+    'big_ln':                    dict(dx=2.2, dweight=0.51, dbias=0.15, dgamma=0.16, dbeta=0.087),      # measured 2.102, 0.503, 0.1451, 0.1559, 0.08643
+    'big_ln_gelu':               dict(dx=1.7, dweight=0.74, dbias=0.27, dgamma=0.089, dbeta=0.12),      # measured 1.639, 0.7382, 0.2612, 0.08821, 0.1185
+    'big_res':                   dict(dx=2.7, dweight=0.75, dbias=0.17),      # measured 2.68, 0.7492, 0.1697
+    'big_deep_res':              dict(dx=2.4, dweight=1.5, dbias=0.25),      # measured 2.389, 1.446, 0.2496
+    'w_rows_span':               dict(dx=9.4, dweight=3.8, dbias=0.66),      # measured 9.359, 3.723, 0.6561
+    'w_rows_span_ln_gelu':       dict(dx=450.0, dweight=670.0, dbias=210.0, dgamma=44, dbeta=18),      # measured 447, 664.3, 207.8, 43.62, 17.66
+    'x_and_w_span':              dict(dx=9.5, dweight=11),      # measured 9.475, 10.97
+    'long_m':                    dict(dx=2.1, dweight=0.22, dbias=0.045, dgamma=0.36, dbeta=0.16),      # measured 2.06, 0.2118, 0.0444, 0.3569, 0.1566
+    'cot_rows_span':             dict(dx=4.7, dweight=11, dbias=2.1),      # measured 4.629, 10.42, 2.094
+    'cot_outlier_column':        dict(dx=17, dweight=4, dbias=0.73, dgamma=2.6, dbeta=2),      # measured 16.27, 3.922, 0.722, 2.58, 1.94
+    'cot_zero_rows':             dict(dx=1, dweight=4.7, dbias=2.1, dgamma=0.23, dbeta=0.18),      # measured 0.9965, 4.658, 2.041, 0.2218, 0.1785
+    'x_rows_span_wgrad':         dict(dx=3.7, dweight=11, dbias=0.78),      # measured 3.622, 10.07, 0.7789
+    'x_cols_span_wgrad':         dict(dx=3.5, dweight=3.7, dbias=0.69),      # measured 3.44, 3.665, 0.6887
+}
+# a-priori terms of the format per case and gradient, in units of 2^-24 n (profiles/image_gemm_units.md); never fitted to a measured q
+FORMAT_TERM = {}
 
 # SwinBlock (the BLOCK_CASES of _swin_linear_ref64): the torch block's float32 backward on the CPU against float64 autograd of
 # block_ref64, per case and per gradient (x and every parameter), rounded up to two digits
@@ -163,6 +223,10 @@ def inputs(name):
         g, beta = 1.0 + 0.1 * R._randn(rs, c.K), 0.1 * R._randn(rs, c.K)
     else:
         res = R._randn(rs, c.M, c.N)
+    if c.special == 'x_rows_span':
+        x = x * R.span(c.M).view(-1, 1)
+    elif c.special == 'x_cols_span':
+        x = x * R.span(c.K).view(1, -1)
     return dict(x=x, weight=w, bias=b, gamma=g, beta=beta, residual=res)
 
 
@@ -173,7 +237,7 @@ def cotangent(name):
     rs = np.random.RandomState(7000 + c.seed)
     g = R._randn(rs, c.M, c.N)
     if c.special == 'cot_rows_span':
-        g = g * torch.pow(2.0, (torch.arange(c.M) % 25 - 12).float()).view(-1, 1)
+        g = g * R.span(c.M).view(-1, 1)
     elif c.special == 'cot_outlier_column':
         g[:, OUTLIER_COLUMN] *= 2.0 ** 10
     elif c.special == 'cot_zero_rows':
@@ -242,6 +306,66 @@ def check(name, got, say=None):
             print('%s %s: %s %.3e, bound %.3e (4 x floor %.1e)' % (name, k, say, err, 4 * floor, floor))
         assert err <= 4 * floor, (name, k, err)
     return errs
+
+
+# ------------------------------------------------------------------------------------------ the unit, per element
+@functools.lru_cache(maxsize=None)
+def normaliser(name):
+    """{gradient name: float64 normaliser of reference(name)[gradient], or None}: every form is written out in the module docstring
+    (THE UNIT); computed once and shared (do not modify)"""
+    c = CASES[name]
+    i = {k: None if v is None else v.double() for k, v in inputs(name).items()}
+    x, W, g = i['x'], i['weight'], cotangent(name).double().abs()
+    n = dict.fromkeys(GRADS)
+    if c.role == 'res':
+        n['dx'], n['dweight'] = g @ W.abs(), g.t() @ x.abs()
+        n['dbias'] = None if i['bias'] is None else g.sum(0)
+        return n
+    gamma, beta = i['gamma'], i['beta']
+    n_xhat, n_t = R.ln_normaliser64(x, gamma, beta, R.EPS)
+    r = 1.0 / torch.sqrt(((x - x.mean(-1, keepdim=True)) ** 2).mean(-1, keepdim=True) + R.EPS)
+    if c.role == 'ln_gelu':
+        y = R.layer_norm64(x, gamma, beta, R.EPS) @ W.t()
+        g = g * R.gelu_grad64(y if i['bias'] is None else y + i['bias']).abs()      # |g_pre|
+    n['dweight'] = g.t() @ n_t
+    n['dbias'] = None if i['bias'] is None else g.sum(0)
+    n_dt = g @ W.abs()
+    n['dbeta'], n['dgamma'] = n_dt.sum(0), (n_dt * n_xhat).sum(0)
+    n_dxhat = n_dt * gamma.abs()
+    n['dx'] = r * (n_dxhat + n_dxhat.mean(-1, keepdim=True) + n_xhat * (n_dxhat * n_xhat).mean(-1, keepdim=True))
+    return n
+
+
+def q_errors(name, got):
+    """{gradient name: per-element q tensor} over the gradients the case has (dresidual: exactly the cotangent, not scored)"""
+    ref, n = reference(name), normaliser(name)
+    out = {}
+    for k in GRADS:
+        if ref[k] is None:
+            assert got.get(k) is None, (name, k)
+            continue
+        assert got[k] is not None and tuple(got[k].shape) == tuple(ref[k].shape), (name, k)
+        if k != 'dresidual':
+            out[k] = R.q_of(got[k].cpu(), ref[k], n[k])
+    return out
+
+
+def bound(name, k):
+    return 2.0 * Q32[name][k] + 1.0 + FORMAT_TERM.get(name, {}).get(k, 0.0)
+
+
+def check_units(name, got, say):
+    """got: {gradient name: tensor or None} of a case in per-element units under bound(name, gradient); prints every figure, then
+    asserts; returns {gradient: (worst, mean) q}"""
+    figures = {k: (float(q.max()), float(q.mean())) for k, q in q_errors(name, got).items()}
+    for k, (worst, mean) in figures.items():
+        print('%s %s: %s worst q %.3f, mean q %.3f, Q32 %.2f, bound %.2f' % (name, k, say, worst, mean, Q32[name][k], bound(name, k)))
+    if reference(name)['dresidual'] is not None:
+        print('%s dresidual: bound: exactly the cotangent' % name)
+        assert torch.equal(got['dresidual'].cpu(), cotangent(name)), (name, 'dresidual')
+    for k, (worst, mean) in figures.items():
+        assert worst <= bound(name, k), (name, k, worst, bound(name, k))
+    return figures
 
 
 # ------------------------------------------------------------------------------------------ the block

@@ -21,8 +21,30 @@ torch.autocast('cpu', torch.bfloat16) for the bf16 cases -- measured by tests/te
 path stays under each entry (rounded up to two digits) and reaches at least half of it: never taken from the kernel.  The factor
 covers a different summation order, the matrix-core products and the device's erf.  No element is excluded.
 
+THE UNIT.  The figure above divides by the tensor's largest element, so an error in a small row or column vanishes in it (dropping
+x W^T from the 16 rows of rows_span whose scale is <= 2^-9 moves it to 5.0e-07 against a bound of 2.44e-06;
+tests/test_swin_linear_cpu.py::test_the_unit_sees_what_the_tensor_maximum_hides).  Every case is therefore ALSO scored per element,
+    q = |out - out64| / (U n),      U = 2^-24 (2^-9 for the bf16 cases),
+where n is the float64 formula of the output with every product of leaves replaced by the product of their absolute values and every
+addition or subtraction by an addition (as tests/_infer_ref64.py does on the voxel side):
+    role res               n = |x| |W|^T + |b| + |residual|
+    roles ln, ln_gelu      n_t = (|x| + |mean|) / sqrt(var + eps) * |gamma| + |beta|   (the cancellation in x - mean shows)
+                           n_pre = n_t |W|^T + |b|
+    after the GELU         n = |gelu'(y64)| n_pre + |gelu(y64)|,   y64 the float64 pre-activation
+float32 cannot hold 1 + erf(y / sqrt 2) below 2^-25, so in the GELU's negative tail the torch path itself is thousands of these units
+off (Q32 of gelu_tails is 2.2e5: the float32 result is an exact zero there) and 2 Q32 + 1 says little about the other elements of such
+a case.  The 'ln_gelu' cases are therefore scored a second time against n_sum, the same n with the GELU's own sum taken as a sum,
+    n_sum = |gelu'(y64)| n_pre + 0.5 |y64| (1 + |erf(y64 / sqrt 2)|),      max q <= 2 Q32_SUM[case] + 1,
+which shows that cancellation as n_t shows the LayerNorm's; both bounds hold.
+An element with n == 0 must be reproduced exactly.  The bound is max q <= 2 Q32[case] + 1 + FORMAT_TERM.get(case, 0): Q32 is the
+worst q of the same torch path as above (float32, or autocast for bf16) on the CPU, rounded up to two digits, asserted by
+tests/test_swin_linear_cpu.py like FLOORS; FORMAT_TERM holds a-priori terms only (profiles/image_gemm_units.md).  The cases
+w_rows_span, w_rows_span_ln_gelu and x_and_w_span aim at the exponents the kernel takes per weight row and per token row: in
+x_and_w_span the residual of element (i, n) carries both scales, so every element is judged at its own size.
+
 Nothing above the harness line calls project code."""
 import collections
+import contextlib
 import functools
 import math
 
@@ -69,6 +91,10 @@ CASES = collections.OrderedDict([
     ('big_deep_res', _c('res', 2069, 1040, 1024, seed=20)),                          # 128 x 64 tile, sums in blocks of K = 1024
     ('bf16_big_ln', _c('ln', 5541, 128, 384, 'bf16', seed=17)),
     ('bf16_big_res', _c('res', 4133, 48, 528, 'bf16', seed=19)),
+    # the exponents (see THE UNIT): weight row n scaled by 2^((n % 25) - 12), alone and against spanned token rows
+    ('w_rows_span', _c('res', 96, 256, 256, seed=21, special='w_rows_span')),
+    ('w_rows_span_ln_gelu', _c('ln_gelu', 64, 128, 512, seed=22, special='w_rows_span')),
+    ('x_and_w_span', _c('res', 96, 256, 256, seed=23, bias=False, special='x_and_w_span')),      # residual (i, n) scaled by both
 ])
 DEGENERATE_ROW = 3
 EPS = 1e-5
@@ -101,7 +127,57 @@ FLOORS = {
     'big_deep_res': 4.4e-07,                 # measured 4.328e-07
     'bf16_big_ln': 3.8e-03,                  # measured 3.704e-03
     'bf16_big_res': 3.1e-03,                 # measured 3.098e-03
+    'w_rows_span': 3.6e-07,                  # measured 3.568e-07
+    'w_rows_span_ln_gelu': 4.2e-07,          # measured 4.167e-07
+    'x_and_w_span': 2.4e-07,                 # measured 2.364e-07
 }
+
+# worst q of the same torch path in the units of THE UNIT (2^-24 n; 2^-9 n for the bf16 cases), rounded up to two digits
+U = 2.0 ** -24
+Q32 = {
+    'qkv_tile': 4.2,                         # measured 4.152, mean 0.295
+    'm_tail': 2200.0,                        # measured 2128, mean 0.669
+    'toy_narrow_qkv': 3.2,                   # measured 3.181, mean 0.349
+    'toy_narrow_proj': 2.2,                  # measured 2.136, mean 0.311
+    'toy_narrow_fc1': 610.0,                 # measured 605.3, mean 0.757
+    'toy_narrow_fc2': 2.4,                   # measured 2.324, mean 0.277
+    'k_deep_res': 0.8,                       # measured 0.7909, mean 0.113
+    'wide_n_gelu': 740.0,                    # measured 730.3, mean 0.305
+    'rows_span': 3.9,                        # measured 3.898, mean 0.309
+    'outlier_channel_res': 27,               # measured 26.86, mean 2.596
+    'outlier_channel_ln': 13,                # measured 12.43, mean 1.039
+    'range_2m12': 3.5,                       # measured 3.486, mean 0.310
+    'range_2p8': 3.5,                        # measured 3.486, mean 0.310
+    'degenerate_rows_ln': 2.9,               # measured 2.843, mean 0.295
+    'degenerate_rows_res': 3.7,              # measured 3.665, mean 0.312
+    'gelu_tails': 220000.0,                  # measured 2.115e+05, mean 586.849
+    'no_ln_bias_zero': 3.4,                  # measured 3.361, mean 0.305
+    'bf16_qkv_tile': 0.9,                    # measured 0.8943, mean 0.135
+    'bf16_m_tail': 0.98,                     # measured 0.9734, mean 0.152
+    'bf16_k_deep_res': 0.17,                 # measured 0.1654, mean 0.023
+    'big_ln': 5,                             # measured 4.963, mean 0.299
+    'big_ln_gelu': 32000.0,                  # measured 3.19e+04, mean 0.723
+    'big_res': 4.8,                          # measured 4.752, mean 0.300
+    'big_deep_res': 2.3,                     # measured 2.295, mean 0.203
+    'bf16_big_ln': 1.2,                      # measured 1.124, mean 0.134
+    'bf16_big_res': 1.6,                     # measured 1.539, mean 0.177
+    'w_rows_span': 3.9,                      # measured 3.876, mean 0.311
+    'w_rows_span_ln_gelu': 170000.0,         # measured 1.66e+05, mean 451.924
+    'x_and_w_span': 3.2,                     # measured 3.179, mean 0.313
+}
+# the 'ln_gelu' cases against n_sum (THE UNIT): worst q of the same torch path, rounded up to two digits
+Q32_SUM = {
+    'm_tail': 4.3,                           # measured 4.245, mean 0.245
+    'toy_narrow_fc1': 2.6,                   # measured 2.55, mean 0.274
+    'wide_n_gelu': 4.1,                      # measured 4.052, mean 0.182
+    'gelu_tails': 4.6,                       # measured 4.518, mean 0.315
+    'bf16_m_tail': 0.98,                     # measured 0.9734, mean 0.120
+    'big_ln_gelu': 4.9,                      # measured 4.86, mean 0.243
+    'w_rows_span_ln_gelu': 4.3,              # measured 4.235, mean 0.219
+}
+# a-priori terms of the format, in units of U n, for cases the kernel's path exceeds 2 Q32 + 1 on by construction; derivations in
+# profiles/image_gemm_units.md.  Never fitted to a measured q
+FORMAT_TERM = {}
 
 # SwinBlock cases of the GPU test (B, H, W, C, heads, ffn, ws, shifted): padded maps, shifted and unshifted; the floor is the torch
 # block in float32 on the CPU against block_ref64, rounded up to two digits
@@ -136,6 +212,11 @@ def _randn(rs, *shape):
     return torch.from_numpy(rs.standard_normal(shape).astype(np.float32))
 
 
+def span(n):
+    """the scale of row i of a *_span case: 2^((i % 25) - 12), exact in float32"""
+    return torch.pow(2.0, (torch.arange(n) % 25 - 12).float())
+
+
 @functools.lru_cache(maxsize=None)
 def inputs(name):
     """dict(x (M, K), weight (N, K), bias (N) or None, gamma, beta (K) or None, residual (M, N) or None): float32 CPU tensors.  In a
@@ -152,13 +233,18 @@ def inputs(name):
     else:
         res = _randn(rs, c.M, c.N)
     if c.special == 'rows_span':
-        x = x * torch.pow(2.0, (torch.arange(c.M) % 25 - 12).float()).view(-1, 1)
+        x = x * span(c.M).view(-1, 1)
     elif c.special == 'outlier':
         x[:, 7] *= 2.0 ** 10
     elif c.special == 'const_row':
         x[DEGENERATE_ROW] = 0.75
     elif c.special == 'zero_row':
         x[DEGENERATE_ROW] = 0.0
+    elif c.special == 'w_rows_span':
+        w = w * span(c.N).view(-1, 1)
+    elif c.special == 'x_and_w_span':                      # every output element is a small row met by a small column, at its own size
+        x, w = x * span(c.M).view(-1, 1), w * span(c.N).view(-1, 1)
+        res = res * span(c.M).view(-1, 1) * span(c.N).view(1, -1)
     if c.x_scale != 1.0:                                   # exact: powers of two
         x = x * c.x_scale
         b = None if b is None else b * c.x_scale
@@ -255,6 +341,107 @@ def torch_path(name, dtype=None):
 
 def out_dtype(case):
     return torch.bfloat16 if case.dtype == 'bf16' and case.role != 'res' else torch.float32
+
+
+# ------------------------------------------------------------------------------------------------------- the unit, per element
+def gelu_grad64(y):
+    """d/dy of gelu64: Phi(y) + y phi(y)"""
+    return 0.5 * (1.0 + torch.erf(y / math.sqrt(2.0))) + y * torch.exp(-0.5 * y * y) / math.sqrt(2.0 * math.pi)
+
+
+def ln_normaliser64(x, gamma, beta, eps):
+    """(n_xhat, n_t) of a LayerNorm in double: (|x| + |mean|) / sqrt(var + eps), and that times |gamma| plus |beta|"""
+    mean = x.mean(-1, keepdim=True)
+    var = ((x - mean) ** 2).mean(-1, keepdim=True)
+    n_xhat = (x.abs() + mean.abs()) / torch.sqrt(var + eps)
+    return n_xhat, n_xhat * gamma.abs() + beta.abs()
+
+
+def linear_normaliser64(role, x, weight, bias, gamma=None, beta=None, residual=None, eps=EPS, gelu_sum=False):
+    """n of one role (THE UNIT): linear_ref64 with every product of leaves taken of absolute values and every sum as a sum; gelu_sum:
+    the GELU's own sum 1 + erf likewise, as 1 + |erf| (n_sum of THE UNIT)"""
+    d = lambda t: None if t is None else t.double()
+    x, weight, bias, gamma, beta, residual = d(x), d(weight), d(bias), d(gamma), d(beta), d(residual)
+    if role == 'res':
+        n = x.abs() @ weight.abs().t()
+    else:
+        n = ln_normaliser64(x, gamma, beta, eps)[1] @ weight.abs().t()
+    if bias is not None:
+        n = n + bias.abs()
+    if role == 'ln_gelu':
+        y = layer_norm64(x, gamma, beta, eps) @ weight.t()
+        y = y if bias is None else y + bias
+        value = 0.5 * y.abs() * (1.0 + torch.erf(y / math.sqrt(2.0)).abs()) if gelu_sum else gelu64(y).abs()
+        n = gelu_grad64(y).abs() * n + value
+    if role == 'res':
+        n = n + residual.abs()
+    return n
+
+
+@functools.lru_cache(maxsize=None)
+def normaliser(name):
+    """the float64 normaliser of a case, the shape of reference(name), computed once and shared (do not modify)"""
+    return linear_normaliser64(CASES[name].role, **inputs(name))
+
+
+@functools.lru_cache(maxsize=None)
+def normaliser_sum(name):
+    """n_sum of a 'ln_gelu' case (THE UNIT), computed once and shared (do not modify)"""
+    assert CASES[name].role == 'ln_gelu', name
+    return linear_normaliser64('ln_gelu', gelu_sum=True, **inputs(name))
+
+
+def unit(name):
+    return 2.0 ** -9 if CASES[name].dtype == 'bf16' else U
+
+
+@contextlib.contextmanager
+def one_thread():
+    """a CPU measurement that gives the same figure on every machine: torch picks a GEMM's blocking, and so the order of its sums, by
+    the thread count"""
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(threads)
+
+
+def q_of(got, ref, n, u=U):
+    """per-element q = |got - ref| / (u n) in double; where n == 0 the element must be reproduced exactly (q = inf otherwise); a NaN
+    counts as inf"""
+    err = (got.double() - ref).abs()
+    err = torch.where(torch.isnan(err), torch.full_like(err, float('inf')), err)
+    return torch.where(n > 0, err / (u * n.clamp_min(1e-300)), torch.where(err > 0, torch.full_like(err, float('inf')), err))
+
+
+def round11(t):
+    """a float64 copy rounded to 11 significant bits: what an operand is without its lo plane"""
+    m, e = torch.frexp(t.double())
+    return torch.ldexp(torch.round(m * 2048.0) / 2048.0, e)
+
+
+LOW_SCALE = 2.0 ** -9                  # the rows and columns of a *_span case with a scale up to this are its low-magnitude ones
+
+
+def bound(name):
+    return 2.0 * Q32[name] + 1.0 + FORMAT_TERM.get(name, 0.0)
+
+
+def check_units(name, out, say):
+    """a case's output in per-element units against bound(name); prints the figures before it asserts; returns (worst, mean) q"""
+    q = q_of(out.cpu(), reference(name), normaliser(name), unit(name))
+    worst, mean = float(q.max()), float(q.mean())
+    print('%s: %s worst q %.3f, mean q %.3f, Q32 %.2f, bound %.2f (unit 2^%d n)' % (name, say, worst, mean, Q32[name], bound(name),
+                                                                                 round(math.log2(unit(name)))))
+    assert worst <= bound(name), (name, worst, bound(name))
+    if CASES[name].role == 'ln_gelu':
+        qs = q_of(out.cpu(), reference(name), normaliser_sum(name), unit(name))
+        b = 2.0 * Q32_SUM[name] + 1.0
+        print('%s: %s against n_sum worst q %.3f, mean q %.3f, Q32_SUM %.2f, bound %.2f' % (name, say, float(qs.max()), float(qs.mean()),
+                                                                                          Q32_SUM[name], b))
+        assert float(qs.max()) <= b, (name, float(qs.max()), b)
+    return worst, mean
 
 
 # ------------------------------------------------------------------------------------ harness (project code from here on)

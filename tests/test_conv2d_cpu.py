@@ -1,5 +1,6 @@
 """The FPN_LSS / DepthNet convolutions (pw_conv2d*, ops.conv2d, conv_impl='hip') on the CPU side: the float64 yardstick of
-tests/_conv2d_ref64.py against F.conv2d + F.batch_norm in double, the FLOORS tables against the torch path (met, and not loose), the
+tests/_conv2d_ref64.py against F.conv2d + F.batch_norm in double, the FLOORS and Q32 tables against the torch path (met, and not loose), the per-element unit against the tensor maximum on a
+spoilt reference, the
 header's ABI rules, refusals before any HIP call, and the module plumbing."""
 import ctypes
 import re
@@ -7,8 +8,10 @@ import re
 import pytest
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 import _conv2d_ref64 as R
+import _swin_linear_ref64 as L
 from preworld_amd import _lib, image_encoder as IE, ops
 
 NAMES = list(R.CASES)
@@ -33,6 +36,93 @@ def test_floor_of_the_torch_path(name):
     print('%s: torch path %.3e, floor %.1e' % (name, err, R.FLOORS[name]))
     assert 0.5 * R.FLOORS[name] <= err <= R.FLOORS[name], (name, err)
     assert set(R.FLOORS) == set(R.CASES)
+
+
+@pytest.mark.parametrize('name', NAMES)
+def test_q32_of_the_torch_path(name):
+    """Q32[name] bounds the worst per-element q of the float32 torch path from above, by less than a factor of two; the normaliser is
+    at least |out64| everywhere, as a sum of absolute values must be"""
+    ref, n = R.reference(name), R.normaliser(name)
+    assert n.dtype == torch.float64 and tuple(n.shape) == tuple(ref.shape) and bool((n >= ref.abs() * (1 - 1e-12)).all())
+    with R.one_thread():
+        q = R.q_of(R.torch_path(name), ref, n)
+    worst = float(q.max())
+    print('%s: torch path worst q %.4g, mean q %.3f, Q32 %.2f, bound %.2f, variant %s' % (name, worst, float(q.mean()), R.Q32[name],
+                                                                                     R.bound(name), R.tile_variant(R.CASES[name])))
+    assert 0.5 * R.Q32[name] <= worst <= R.Q32[name], (name, worst)
+    assert set(R.Q32) == set(R.CASES) and set(R.FORMAT_TERM) <= set(R.CASES)
+
+
+def test_the_fold_of_the_normaliser_is_the_yardsticks():
+    """fold64 restates the BatchNorm and bias as scale and shift: conv(x, w) scale + shift (+ residual, ReLU) is the yardstick"""
+    for name in ('bn_fold', 'res_relu', 'cout_88_1x1', 'bn_scale_span', 'dim_image'):
+        c, i = R.CASES[name], R.inputs(name)
+        scale, shift = R.fold64(name)
+        y = F.conv2d(i['x'].double(), i['weight'].double(), None, padding=R.padding(c), dilation=c.dil)
+        y = y * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
+        y = y if i['residual'] is None else y + i['residual'].double()
+        y = y if c.epi == 'none' else y.clamp_min(0.0)
+        assert R.rel_err(y, R.reference(name)) < 1e-12, name
+
+
+def test_exponent_cases_are_what_they_claim():
+    C, i = R.CASES, R.inputs
+    c, x = C['dim_image'], i('dim_image')['x']
+    assert (c.B, c.H, c.W, c.Cin, c.Cout, c.k, c.dil) == (2, 7, 9, 64, 64, 3, 1) and not c.bn and not c.bias and c.epi == 'none'
+    assert 2.0 ** -14.5 < float(x[1].abs().max() / x[0].abs().max()) < 2.0 ** -13.5
+    n = R.normaliser('dim_image')
+    assert float(n[0].min() / n[1].max()) > 2.0 ** 10                # the whole second image lies far below the first
+    c, x = C['dim_corner'], i('dim_corner')['x']
+    assert (c.B, c.H, c.W, c.Cin, c.Cout, c.k, c.dil) == (1, 20, 15, 32, 16, 3, 6)
+    assert float(x[:, :, :6].abs().max()) < 2.0 ** -11 and float(x[:, :, 6:].abs().max()) > 2.0
+    c, w = C['w_rows_span'], i('w_rows_span')['weight']
+    assert (c.H, c.W, c.Cin, c.Cout, c.k) == (9, 11, 32, 88, 3) and c.Cout % 64 and not c.bn and not c.bias
+    amax = w.abs().amax((1, 2, 3))
+    assert 2.0 ** 11.5 < float(amax[12] / amax[0]) < 2.0 ** 12.5 and float(amax.max() / amax.min()) > 2.0 ** 22
+    c = C['bn_scale_span']
+    assert (c.H, c.W, c.Cin, c.Cout, c.k) == (9, 11, 32, 32, 3) and c.bn
+    scale, shift = R.fold64('bn_scale_span')
+    assert 2.0 ** 9 < float(scale.abs().max() / scale.abs().min()) < 2.0 ** 12 and float(scale.abs().max()) < 2.5
+    assert float((shift.abs() / scale.abs()).max() / (shift.abs() / scale.abs()).min()) < 2.0 ** 9      # the shift follows the scale
+
+
+@pytest.mark.parametrize('name', ['dim_image', 'w_rows_span'])
+def test_the_unit_sees_what_the_tensor_maximum_hides(name):
+    """the yardstick against itself: the float64 output spoilt where it is small stays under the tensor-maximum bound 4 x FLOORS and
+    is far over the per-element bound, which the clean float32 torch path meets.  w_rows_span: the output channels whose weight scale
+    is <= 2^-9 lose the whole sum, or have their weights rounded to 11 significant bits (a lost lo plane).  dim_image: the second
+    image's input is rounded to 11 significant bits; the tensor maximum does see that whole image vanish (2^-14 of the largest
+    element against a bound near 2^-20; printed), so the sum is dropped from those of its elements that lie below 2^-20 of the
+    largest -- which it cannot see either"""
+    c, i, ref, n = R.CASES[name], R.inputs(name), R.reference(name), R.normaliser(name)
+    x, w = i['x'].double(), i['weight'].double()
+    dropped = ref.clone()
+    if name == 'dim_image':
+        whole = ref.clone()
+        whole[1] = 0.0
+        print('%s, the whole second image dropped: tensor-max %.3e (bound %.3e)' % (name, R.rel_err(whole, ref), 4 * R.FLOORS[name]))
+        low = ref.abs() <= 2.0 ** -20 * ref.abs().max()
+        low[0] = False
+        assert 20 <= int(low.sum()) and R.rel_err(whole, ref) > 4 * R.FLOORS[name]
+        dropped[low] = 0.0
+        x = x.clone()
+        x[1] = L.round11(x[1])
+        where = '%d elements of the second image' % int(low.sum())
+    else:
+        low = torch.pow(2.0, (torch.arange(c.Cout) % 25 - 12).float()) <= L.LOW_SCALE
+        assert 0 < int(low.sum()) < c.Cout // 2
+        dropped[:, low] = 0.0
+        w = torch.where(low.view(-1, 1, 1, 1), L.round11(w), w)
+        where = '%d low channels' % int(low.sum())
+    rounded = F.conv2d(x, w, None, padding=R.padding(c), dilation=c.dil)
+    for what, out in (('the sum dropped in ' + where, dropped), ('11 significant bits', rounded)):
+        old, q = R.rel_err(out, ref), float(R.q_of(out, ref, n).max())
+        print('%s, %s: tensor-max %.3e (bound %.3e), worst q %.4g (bound %.2f)' % (name, what, old, 4 * R.FLOORS[name], q, R.bound(name)))
+        assert 0.0 < old <= 4 * R.FLOORS[name], (name, what, old)
+        assert q > 10 * R.bound(name), (name, what, q)
+    with R.one_thread():
+        clean = float(R.q_of(R.torch_path(name), ref, n).max())
+    assert clean <= R.bound(name), (name, clean)
 
 
 def test_module_floors():

@@ -1,5 +1,5 @@
 """The FPN_LSS / DepthNet convolutions on the device: pw_conv2d through ops.conv2d against the float64 yardstick of
-tests/_conv2d_ref64.py under 4 x the torch path's own CPU floor, exact scaling of the range cases, same bits twice, graph capture, a
+tests/_conv2d_ref64.py under 4 x the torch path's own CPU floor and, per element in units of 2^-24 n, under 2 Q32 + 1, exact scaling of the range cases, same bits twice, graph capture, a
 refused layout, FPN_LSS / DepthNet(conv_impl='hip') against the golden outputs and, at real width, against the float64 modules, the
 Derived cache after new BatchNorm statistics, and the image branch with fused convolutions against the torch branch."""
 import numpy as np
@@ -46,6 +46,15 @@ def test_ops_against_the_yardstick(name):
                                                                         R.tile_variant(R.CASES[name])))
     assert bool(torch.isfinite(out).all())
     assert err <= 4 * R.FLOORS[name], (name, err)
+
+
+@pytest.mark.parametrize('name', NAMES)
+def test_ops_per_element_units(name):
+    """every element against its own magnitude: q = |out - out64| / (2^-24 n) under 2 Q32 + 1 + FORMAT_TERM (THE UNIT in
+    tests/_conv2d_ref64.py); an element whose normaliser is zero must be exact"""
+    out, _ = _run(name)
+    assert out.dtype == torch.float32 and bool(torch.isfinite(out).all())
+    R.check_units(name, out, 'kernel')
 
 
 def test_range_cases_scale_exactly():

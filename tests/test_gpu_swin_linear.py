@@ -1,5 +1,5 @@
 """The Swin blocks' fused Linears on the device: pw_swin_linear through ops.swin_linear against the float64 yardstick of
-tests/_swin_linear_ref64.py under 4 x the torch modules' own CPU floor, SwinBlock(linear_impl='hip') against the float64 block, whole
+tests/_swin_linear_ref64.py under 4 x the torch modules' own CPU floor and, per element in units of 2^-24 n, under 2 Q32 + 1, SwinBlock(linear_impl='hip') against the float64 block, whole
 models against the golden outputs and against 'torch' Linears, same bits twice, graph capture, the Derived cache after an in-place
 update, the torch path under grad, and a NaN that stays in its row."""
 import numpy as np
@@ -53,6 +53,15 @@ def test_ops_against_the_yardstick(name):
         row_err = float((out[r].double().cpu() - ref[r]).abs().max() / ref.abs().max())
         print('%s: degenerate row %.3e' % (name, row_err))
         assert row_err <= 4 * R.FLOORS[name]
+
+
+@pytest.mark.parametrize('name', NAMES)
+def test_ops_per_element_units(name):
+    """every element against its own magnitude: q = |out - out64| / (U n) under 2 Q32 + 1 + FORMAT_TERM (THE UNIT in
+    tests/_swin_linear_ref64.py); an element whose normaliser is zero must be exact"""
+    out, _ = _run(name)
+    assert out.dtype == R.out_dtype(R.CASES[name]) and bool(torch.isfinite(out).all())
+    R.check_units(name, out, 'kernel')
 
 
 def test_range_cases_scale_exactly():

@@ -1,6 +1,7 @@
 """The backward of the fused Swin Linears on the device: include/preworld_hip_swin_linear_bwd.h through ops.SwinLinear /
 ops.swin_linear_backward and through SwinBlock(attn_impl='hip_grad', linear_impl='hip_grad') against the float64 autograd yardstick of
-tests/_swin_linear_bwd_ref64.py under 4 x the torch path's own CPU floors; the forward's bits, same bits twice, the need_* switches,
+tests/_swin_linear_bwd_ref64.py under 4 x the torch path's own CPU floors and, per element in units of 2^-24 n, under 2 Q32 + 1; the
+forward's bits, same bits twice, the need_* switches,
 graph capture, an in-place weight update, the toy Swin against the torch path and bf16 autocast."""
 import numpy as np
 import pytest
@@ -52,6 +53,14 @@ def test_gradients_against_the_yardstick(name):
     G.check(name, got, say='kernel')
     if name == 'cot_zero_rows':
         assert float(got['dx'][G.ZERO_ROW].abs().max()) == 0.0      # an all-zero cotangent row: exact zeros
+
+
+@pytest.mark.parametrize('name', list(G.CASES))
+def test_gradients_per_element_units(name):
+    """every element of every gradient against its own magnitude: q = |g - g64| / (2^-24 n) under 2 Q32 + 1 + FORMAT_TERM (THE UNIT in
+    tests/_swin_linear_bwd_ref64.py); dresidual is exactly the cotangent, a zero normaliser asks for an exact zero"""
+    _, got = _function_grads(name)
+    G.check_units(name, got, 'kernel')
 
 
 @pytest.mark.parametrize('name', ['qkv_tile', 'm_tail', 'wide_n_gelu'])

@@ -1,5 +1,6 @@
 """CPU side of the fused Swin Linears' backward: the float64 yardstick of tests/_swin_linear_bwd_ref64.py against the torch modules in
-double, the float32 floors of the torch path it sets for the kernels, the case census, the C ABI of
+double, the float32 floors of the torch path it sets for the kernels (tensor maximum and per element), the per-element unit
+against the tensor maximum on a spoilt reference, the case census, the C ABI of
 include/preworld_hip_swin_linear_bwd.h (parsing, refusals before any HIP call) and the linear_impl='hip_grad' plumbing."""
 import ctypes
 import re
@@ -41,6 +42,47 @@ def test_floor_of_the_torch_path(name):
         assert 0.5 * floor <= err <= floor, (name, k, err, floor)
 
 
+@pytest.mark.parametrize('name', list(G.CASES))
+def test_q32_of_the_torch_path(name):
+    """Q32[name][gradient] bounds the worst per-element q of the torch modules' float32 backward from above, by less than a factor of
+    two; every normaliser is at least |gradient| everywhere, as a sum of absolute values must be"""
+    got, ref, n = G.torch_path_grads(name), G.reference(name), G.normaliser(name)
+    qs = G.q_errors(name, got)
+    assert set(qs) == set(G.Q32[name]) == set(G.BWD_FLOORS[name]) and set(G.Q32) == set(G.CASES)
+    for k, q in qs.items():
+        assert n[k].dtype == torch.float64 and tuple(n[k].shape) == tuple(ref[k].shape), (name, k)
+        assert bool((n[k] >= ref[k].abs() * (1 - 1e-12)).all()), (name, k)
+        worst = float(q.max())
+        print('%s %s: torch float32 worst q %.4g, mean q %.3f, Q32 %.2f, bound %.2f' % (name, k, worst, float(q.mean()), G.Q32[name][k],
+                                                                                    G.bound(name, k)))
+        assert 0.5 * G.Q32[name][k] <= worst <= G.Q32[name][k], (name, k, worst)
+    G.check_units(name, got, 'torch float32')             # and dresidual is exactly the cotangent
+    if name == 'cot_zero_rows':                           # a zero normaliser: the row must be, and is, exactly zero
+        assert float(n['dx'][G.ZERO_ROW].max()) == 0.0 and float(n['dx'].min()) == 0.0 and float(qs['dx'][G.ZERO_ROW].max()) == 0.0
+
+
+def test_the_unit_sees_what_the_tensor_maximum_hides():
+    """the yardstick against itself on cot_rows_span's data gradient: the float64 dx with the rows whose cotangent scale is <= 2^-9
+    spoilt -- g W dropped there, or the cotangent rounded to 11 significant bits there, a lost lo plane -- stays under the
+    tensor-maximum bound 4 x BWD_FLOORS and is far over the per-element bound, which the clean float32 torch backward meets"""
+    name = 'cot_rows_span'
+    c, ref, n = G.CASES[name], G.reference(name)['dx'], G.normaliser(name)['dx']
+    g, W = G.cotangent(name).double(), G.inputs(name)['weight'].double()
+    low = R.span(c.M) <= R.LOW_SCALE
+    assert int(low.sum()) == 16
+    dropped = ref.clone()
+    dropped[low] = 0.0
+    rounded = torch.where(low.view(-1, 1), R.round11(g), g) @ W
+    for what, out in (('g W dropped', dropped), ('11 significant bits', rounded)):
+        old, q = G.rel_err(out, ref), float(R.q_of(out, ref, n).max())
+        print('%s dx, %s in 16 low rows: tensor-max %.3e (bound %.3e), worst q %.4g (bound %.2f)' % (
+            name, what, old, 4 * G.BWD_FLOORS[name]['dx'], q, G.bound(name, 'dx')))
+        assert 0.0 < old <= 4 * G.BWD_FLOORS[name]['dx'], (what, old)
+        assert q > 10 * G.bound(name, 'dx'), (what, q)
+    clean = float(G.q_errors(name, G.torch_path_grads(name))['dx'].max())
+    assert clean <= G.bound(name, 'dx'), clean
+
+
 @pytest.mark.parametrize('name', list(R.BLOCK_CASES))
 def test_block_yardstick_and_floor(name):
     errs64 = G.block_errors(name, G.block_grads(name, dtype=torch.float64)[2])
@@ -55,7 +97,17 @@ def test_block_yardstick_and_floor(name):
 
 def test_cases_are_what_they_claim():
     C = G.CASES
-    assert [k for k in R.CASES if R.CASES[k].dtype == 'f32'] + list(G.NEW_CASES) == list(C) and len(C) == 25
+    assert [k for k in R.CASES if R.CASES[k].dtype == 'f32'] + list(G.NEW_CASES) == list(C) and len(C) == 30
+    assert {'w_rows_span', 'w_rows_span_ln_gelu', 'x_and_w_span'} <= set(C)          # the forward's exponent cases
+    for name, dim in (('x_rows_span_wgrad', 0), ('x_cols_span_wgrad', 1)):
+        c, x = C[name], G.inputs(name)['x']
+        assert (c.role, c.M, c.K, c.N) == ('res', 96, 256, 256)
+        amax = x.abs().amax(1 - dim)
+        assert 2.0 ** 11.5 < float(amax[12] / amax[0]) < 2.0 ** 12.5 and float(amax.max() / amax.min()) > 2.0 ** 22, name
+        g = G.cotangent(name).abs().amax(1)
+        assert float(g.max() / g.min()) < 2.0, name                                  # a plain cotangent
+    dw = G.reference('x_cols_span_wgrad')['dweight'].abs().amax(0)                   # small columns of dweight
+    assert float(dw.max() / dw.min()) > 2.0 ** 22
     assert all(c.dtype == 'f32' for c in C.values())
     assert {c.role for c in C.values()} == {'ln', 'ln_gelu', 'res'}
     big = lambda M, N: -(-M // 128) * -(-N // 128) >= 128                    # the forward's tile rule, for both GEMMs it serves

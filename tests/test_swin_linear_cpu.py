@@ -1,5 +1,6 @@
 """The Swin blocks' fused Linears (pw_swin_linear*, ops.swin_linear, linear_impl='hip') on the CPU side: the float64 yardstick of
-tests/_swin_linear_ref64.py against the torch modules in double, the FLOORS tables against the torch path (met, and not loose), the
+tests/_swin_linear_ref64.py against the torch modules in double, the FLOORS and Q32 tables against the torch path (met, and not loose), the per-element unit against the tensor maximum on a
+spoilt reference, the
 header's ABI rules, refusals before any HIP call, and the module plumbing."""
 import ctypes
 import re
@@ -33,6 +34,63 @@ def test_floor_of_the_torch_path(name):
     print('%s: torch path %.3e, floor %.1e' % (name, err, R.FLOORS[name]))
     assert 0.5 * R.FLOORS[name] <= err <= R.FLOORS[name], (name, err)
     assert set(R.FLOORS) == set(R.CASES)
+
+
+@pytest.mark.parametrize('name', NAMES)
+def test_q32_of_the_torch_path(name):
+    """Q32[name] (and Q32_SUM for a 'ln_gelu' case) bounds the worst per-element q of the same torch path from above, by less than a
+    factor of two; the normaliser is at least |out64| everywhere, as a sum of absolute values must be"""
+    ref, n = R.reference(name), R.normaliser(name)
+    assert n.dtype == torch.float64 and tuple(n.shape) == tuple(ref.shape) and bool((n >= ref.abs() * (1 - 1e-12)).all())
+    with R.one_thread():
+        out = R.torch_path(name)
+    q = R.q_of(out, ref, n, R.unit(name))
+    worst = float(q.max())
+    print('%s: torch path worst q %.4g, mean q %.3f, Q32 %.2f, bound %.2f' % (name, worst, float(q.mean()), R.Q32[name], R.bound(name)))
+    assert 0.5 * R.Q32[name] <= worst <= R.Q32[name], (name, worst)
+    if R.CASES[name].role == 'ln_gelu':
+        ns = R.normaliser_sum(name)
+        assert bool((ns >= n * (1 - 1e-12)).all())
+        worst = float(R.q_of(out, ref, ns, R.unit(name)).max())
+        print('%s: torch path against n_sum worst q %.4g, Q32_SUM %.2f' % (name, worst, R.Q32_SUM[name]))
+        assert 0.5 * R.Q32_SUM[name] <= worst <= R.Q32_SUM[name], (name, worst)
+    assert set(R.Q32) == set(R.CASES) and set(R.Q32_SUM) == {k for k, c in R.CASES.items() if c.role == 'ln_gelu'}
+    assert set(R.FORMAT_TERM) <= set(R.CASES) and R.unit(name) == (2.0 ** -9 if name.startswith('bf16_') else 2.0 ** -24)
+
+
+def test_q_of_asks_for_an_exact_zero_where_the_normaliser_is_zero():
+    ref, n = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float64), torch.tensor([0.0, 0.0, 2.0], dtype=torch.float64)
+    q = R.q_of(torch.tensor([0.0, 1e-30, 1.0 + 2.0 ** -22]), ref, n)
+    assert float(q[0]) == 0.0 and float(q[1]) == float('inf') and float(q[2]) == 2.0
+    assert float(R.q_of(torch.tensor([float('nan')]), ref[2:], n[2:])) == float('inf')
+
+
+@pytest.mark.parametrize('name,axis', [('rows_span', 'x'), ('w_rows_span', 'weight')])
+def test_the_unit_sees_what_the_tensor_maximum_hides(name, axis):
+    """the yardstick against itself: the float64 output with the rows of x (the columns of the output, for the weight) whose scale is
+    <= 2^-9 spoilt -- x W^T dropped there, or the operand rounded to 11 significant bits there, a lost lo plane -- stays under the
+    tensor-maximum bound 4 x FLOORS and is far over the per-element bound, which the clean float32 torch path meets"""
+    c, ref, n = R.CASES[name], R.reference(name), R.normaliser(name)
+    d = {k: None if v is None else v.double() for k, v in R.inputs(name).items()}
+    low = R.span(c.M if axis == 'x' else c.N) <= R.LOW_SCALE
+    assert 0 < int(low.sum()) < len(low) // 2
+    rest = d['residual'] + d['bias']
+    dropped = ref.clone()
+    if axis == 'x':
+        dropped[low] = rest[low]
+    else:
+        dropped[:, low] = rest[:, low]
+    d[axis] = torch.where(low.view(-1, 1), R.round11(d[axis]), d[axis])
+    rounded = R.linear_ref64(c.role, **d)
+    for what, out in (('x W^T dropped', dropped), ('11 significant bits', rounded)):
+        old, q = R.rel_err(out, ref), float(R.q_of(out, ref, n).max())
+        print('%s, %s in %d low %s: tensor-max %.3e (bound %.3e), worst q %.4g (bound %.2f)' % (
+            name, what, int(low.sum()), 'rows' if axis == 'x' else 'columns', old, 4 * R.FLOORS[name], q, R.bound(name)))
+        assert 0.0 < old <= 4 * R.FLOORS[name], (name, what, old)
+        assert q > 10 * R.bound(name), (name, what, q)
+    with R.one_thread():
+        clean = float(R.q_of(R.torch_path(name), ref, n).max())
+    assert clean <= R.bound(name), (name, clean)
 
 
 @pytest.mark.parametrize('name', list(R.BLOCK_CASES))
@@ -102,6 +160,28 @@ def test_cases_are_what_they_claim():
         assert {big(c) for c in R.CASES.values() if (c.dtype == 'bf16') == bf} == {False, True}
     assert {big(c) for c in R.CASES.values() if c.dtype == 'f32' and c.K > 1024} == {False, True}
     assert any(c.K == 16 for c in R.CASES.values()) and any(c.K == 4096 for c in R.CASES.values()) and any(c.N == 4096 for c in R.CASES.values())
+
+
+def test_span_cases_are_what_they_claim():
+    i, sp = R.inputs, R.span(256)
+    assert float(sp.max() / sp.min()) == 2.0 ** 24 and torch.equal(sp[:25], torch.pow(2.0, torch.arange(-12.0, 13.0)))
+    for name, (role, M, K, N) in (('w_rows_span', ('res', 96, 256, 256)), ('w_rows_span_ln_gelu', ('ln_gelu', 64, 128, 512)),
+                                  ('x_and_w_span', ('res', 96, 256, 256))):
+        c = R.CASES[name]
+        assert (c.role, c.M, c.K, c.N, c.dtype) == (role, M, K, N, 'f32'), name
+        amax = i(name)['weight'].abs().amax(1)
+        assert 2.0 ** 11.5 < float(amax[12] / amax[0]) < 2.0 ** 12.5 and float(amax.max() / amax.min()) > 2.0 ** 22, name
+    amax = i('w_rows_span')['x'].abs().amax(1)
+    assert float(amax.max() / amax.min()) < 2.0                      # only the weight is spanned there
+    d = i('x_and_w_span')
+    amax = d['x'].abs().amax(1)
+    assert float(amax.max() / amax.min()) > 2.0 ** 22 and d['bias'] is None
+    # every element of x_and_w_span is judged at its own size: the normaliser follows the product of the two scales over 2^48 ...
+    n = R.normaliser('x_and_w_span')
+    scale = (R.span(96).view(-1, 1) * R.span(256).view(1, -1)).double()
+    assert float(n.max() / n.min()) > 2.0 ** 44 and float((n / scale).max() / (n / scale).min()) < 64.0
+    # ... while the tensor's largest element is the only size the tensor-maximum figure knows
+    assert float(R.reference('x_and_w_span').abs().max() / n.min()) > 2.0 ** 40
 
 
 # ------------------------------------------------------------------------------------------------------------ ABI
