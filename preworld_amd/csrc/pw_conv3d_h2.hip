@@ -27,7 +27,7 @@ constexpr int H2_LDS = H2_SB_OFF + 2 * H2_MAX_COUT * 4;
 // The tile that finished in stage s is written out DURING stage s+1.  At the end of stage s every wave only parks its raw
 // accumulators in LDS (h2_epi_park: 8 ds_write_b128 per N-tile).  The 4 NT passes that turn them into
 // scale / bias / residual / ReLU / fp16 split / coalesced stores are BRANCH-FREE straight-line code placed in the same
-// scheduling region as the 12 NT MFMAs of taps 2 .. 4 NT + 1 of the next stage (their LDS / residual loads one tap earlier),
+// scheduling region as the 12 NT MFMAs of taps 2 .. 4 NT + 1 of the next stage (their LDS loads one tap earlier, "Residual lead" below),
 // so that they issue in the ~5 free slots a single wave has per 32-cycle MFMA: a separate epilogue phase cost 4.9 k of a
 // 22.9 k-cycle stage, and the same passes placed before the MFMAs (branchy version) simply moved those cycles into the taps.
 // Being branch-free means the variant is a template parameter:
@@ -36,9 +36,33 @@ constexpr int H2_LDS = H2_SB_OFF + 2 * H2_MAX_COUT * 4;
 // A stage with nothing parked runs the same code with every lane's offset out of range (loads return 0, stores are dropped).
 // Parking area = this wave's own halo rows (wave + 4 K, K < 7 / 13 for NT 1 / 2) of the buffer the stage just consumed: those
 // rows are refilled only by this wave's own DMA instructions, which are issued after the passes (other rows first).
+//
+// Residual lead (EPI 2).  A pass's LDS operands (parked row, scale, bias) are read one tap ahead of the pass: ~100 cycles of LDS latency
+// under a ~500-cycle tap.  Its two residual rows come from HBM / L2 (0.9 k cycles unloaded, ~1.3 k under this kernel's traffic)
+// and, with one wave per SIMD, the s_waitcnt in front of the pass stalls the wave's MFMA issue as well.  Loads return in order, so
+// a row requested inside tap T can have two taps at most: the weights requested in tap T are needed in tap T + 2, and waiting for
+// them waits for every load requested before them.  The one long stretch without such a wait is from the stage-end barrier to tap 2
+// of the next stage (the weights of taps 0 and 1 landed before the barrier): the next stage's set-up plus two taps, ~2 k cycles.
+// So the rows are fetched on their own schedule (h2_epi_res_load) into a small register ring, slot = pass % H2_RES_LEAD, and the
+// first H2_RES_LEAD passes' rows are requested in that stretch: half of them right behind h2_epi_park -- the tile's coordinates are
+// known there -- and the other half spread over the next stage's set-up code (h2_epi_res_range; the rest path requests them up
+// front).  Later passes (NT 2 only) refill the slot a pass has just consumed, inside that pass's tap.
+// What stays: the four waves of a block leave the barrier together and their 8 x 1 KB requests each go through the CU's one
+// texture path, ~500 cycles per tile that no MFMA covers, wherever in that stretch they are issued (all behind the park, or
+// staggered as here: the same stage period within 0.3 %).  Requesting the rows under the MFMAs in the middle of the tile's last
+// stage instead was measured as well and gives the cycles back in those taps' weight waits, for the in-order reason above.
+// Per-tap and per-stage figures of the three placements: profiles/conv_residual_prefetch.md.
+// In place (BasicBlock3D: residual == y0) this stays correct: a pass loads and stores only its own 16 voxel rows x its own 32
+// channel columns and tiles are disjoint, so rows requested above the stores of earlier passes are never the rows those stores write.
+#ifndef PW_RES_LEAD
+#define PW_RES_LEAD 4
+#endif
+constexpr int H2_RES_LEAD = PW_RES_LEAD;
+constexpr int H2_RES_AT_PARK = (H2_RES_LEAD + 1) / 2;       // passes requested right behind h2_epi_park; the others during the next set-up
 struct EpiTile { int b, d0, h0, w0, ng; unsigned bufoff; bool pending; };
 struct EpiRegs {
-  v4f x0, x1, s0, s1, b0, b1; float4 r0, r1; unsigned vbase, soff;
+  v4f x0, x1, s0, s1, b0, b1; unsigned vbase, soff;
+  float4 res[H2_RES_LEAD][2];  // EPI 2: residual rows {hi, lo} of passes in flight, slot = pass % H2_RES_LEAD
   float amax0, amax1;        // largest |stored value| written to y0 / y1 (tiles whose passes have completed)
   float amax_nt[2];          // ... by the passes of the tile in flight, per N-tile of the wave: which destination an N-tile
                              // feeds depends on the tile's N-group (wave-uniform), so it is resolved once per tile (epi_fold_amax)
@@ -81,10 +105,10 @@ __device__ __forceinline__ void h2_epi_park(const f32x16 (&acc)[2][NT], char* st
     }
 }
 
-// pass P of 4 NT covers 16 parked voxel rows; lane = (row u = 16 P + (lane >> 2), channel octet o = lane & 3)
+// pass P of 4 NT covers 16 parked voxel rows; lane = (row u = 16 P + (lane >> 2), channel octet o = lane & 3).
+// -> this lane's buffer offsets of the pass in y0 / y1 (and in the residual, which has y0's layout)
 template <int NT, int EPI, int P>
-__device__ __forceinline__ void h2_epi_load(const ConvArgs& a, const EpiTile& t, const char* stg, const float* sb, int wave,
-                                            int lane, EpiRegs& r) {
+__device__ __forceinline__ void h2_epi_addr(const ConvArgs& a, const EpiTile& t, int wave, int lane, unsigned& vbase, unsigned& soff) {
   constexpr int nt = P >> 2;
   const int n0 = (t.ng * NT + nt) * 32;
   const bool to_y0 = n0 < a.cout0;
@@ -96,10 +120,21 @@ __device__ __forceinline__ void h2_epi_load(const ConvArgs& a, const EpiTile& t,
   const int mt = sv >> 5, vr = (sv >> 3) & 3, vc = sv & 7;
   // (no short-circuit: the pass lives inside a tap's scheduling region, a branch would cut that region in two)
   const bool ok = (int)t.pending & (int)(od < a.Do) & (int)((t.h0 + mt * 4 + vr) < a.Ho) & (int)((t.w0 + vc) < a.Wo);
-  r.soff = (unsigned)(((((t.b * a.Do + od) * a.Ho + t.h0) * a.Wo + t.w0) * ld) * 4);
+  soff = (unsigned)(((((t.b * a.Do + od) * a.Ho + t.h0) * a.Wo + t.w0) * ld) * 4);
   const unsigned pos = (EPI == 3 ? (unsigned)(32 * o) : (unsigned)((4 * (o & 1) + 2 * (o >> 1)) * 16));
   const unsigned vin = (unsigned)(((mt * 4 + vr) * a.Wo + vc) * ld) * 4u + (unsigned)col0 * 4u + pos;
-  r.vbase = ok ? vin : PIPE_OOB;
+  vbase = ok ? vin : PIPE_OOB;
+}
+
+// the LDS part of a pass, one tap ahead of it
+template <int NT, int EPI, int P>
+__device__ __forceinline__ void h2_epi_load(const ConvArgs& a, const EpiTile& t, const char* stg, const float* sb, int wave,
+                                            int lane, EpiRegs& r) {
+  constexpr int nt = P >> 2;
+  const int n0 = (t.ng * NT + nt) * 32;
+  const int o = lane & 3;
+  const int u = 16 * P + (lane >> 2);
+  h2_epi_addr<NT, EPI, P>(a, t, wave, lane, r.vbase, r.soff);
   const char* src = stg + epi_slot_off(u);
   const int sw = (u >> 1) & 7;
   r.x0 = *reinterpret_cast<const v4f*>(src + (((2 * o) ^ sw) * 16));
@@ -108,11 +143,32 @@ __device__ __forceinline__ void h2_epi_load(const ConvArgs& a, const EpiTile& t,
   r.s1 = *reinterpret_cast<const v4f*>(sb + n0 + 8 * o + 4);
   r.b0 = *reinterpret_cast<const v4f*>(sb + H2_MAX_COUT + n0 + 8 * o);
   r.b1 = *reinterpret_cast<const v4f*>(sb + H2_MAX_COUT + n0 + 8 * o + 4);
-  if constexpr (EPI == 2) {
-    const unsigned out_vox = (unsigned)((size_t)a.B * a.Do * a.Ho * a.Wo);
-    const rsrc_t rr = make_rsrc(a.residual, out_vox * (unsigned)ld * 4u);
-    r.r0 = buf_load4(rr, r.vbase, r.soff);
-    r.r1 = buf_load4(rr, r.vbase == PIPE_OOB ? PIPE_OOB : r.vbase + 16u, r.soff);
+}
+
+// EPI 2: the residual rows of pass P (8 hi halves, 8 lo halves of this lane's channel octet) -> ring slot P % H2_RES_LEAD.
+// The addresses are those of h2_epi_addr<NT, 2, P> (every column goes to y0: EPI 2 has no y1), split so that all that differs
+// from pass to pass is wave-uniform (the soffset) or one compare (the row test).
+template <int NT, int P>
+__device__ __forceinline__ void h2_epi_res_load(const ConvArgs& a, const EpiTile& t, int wave, int lane, EpiRegs& r) {
+  constexpr int prow = 2 * (P & 3);                 // the pass covers tile rows prow, prow + 1 of N-tile P >> 2
+  const int od = t.d0 + wave;
+  const int o = lane & 3, hr = lane >> 5, vc = (lane >> 2) & 7;
+  const bool ok = (int)t.pending & (int)(od < a.Do) & (int)(hr < a.Ho - t.h0 - prow) & (int)((t.w0 + vc) < a.Wo);
+  const unsigned vlane = (unsigned)((hr * a.Wo + vc) * a.ld0) * 4u + (unsigned)((4 * (o & 1) + 2 * (o >> 1)) * 16);
+  const unsigned soff0 = (unsigned)((((((t.b * a.Do + od) * a.Ho + t.h0) * a.Wo + t.w0) * a.ld0) + t.ng * NT * 32) * 4);
+  const unsigned soff = soff0 + (unsigned)prow * ((unsigned)(a.Wo * a.ld0) * 4u) + (unsigned)((P >> 2) * 128);
+  const unsigned vbase = ok ? vlane : PIPE_OOB;
+  const unsigned out_vox = (unsigned)((size_t)a.B * a.Do * a.Ho * a.Wo);
+  const rsrc_t rr = make_rsrc(a.residual, out_vox * (unsigned)a.ld0 * 4u);
+  r.res[P % H2_RES_LEAD][0] = buf_load4(rr, vbase, soff);
+  r.res[P % H2_RES_LEAD][1] = buf_load4(rr, vbase, soff + 16u);
+}
+// passes P0 .. P1 - 1 of the first H2_RES_LEAD
+template <int NT, int P0, int P1>
+__device__ __forceinline__ void h2_epi_res_range(const ConvArgs& a, const EpiTile& t, int wave, int lane, EpiRegs& r) {
+  if constexpr (P0 < P1 && P0 < H2_RES_LEAD && P0 < 4 * NT) {
+    h2_epi_res_load<NT, P0>(a, t, wave, lane, r);
+    h2_epi_res_range<NT, P0 + 1, P1>(a, t, wave, lane, r);
   }
 }
 
@@ -129,8 +185,8 @@ __device__ __forceinline__ void h2_epi_compute(const ConvArgs& a, const EpiTile&
   float v[8];
 #pragma unroll
   for (int e = 0; e < 4; ++e) { v[e] = fmaf(r.x0[e], r.s0[e], r.b0[e]); v[4 + e] = fmaf(r.x1[e], r.s1[e], r.b1[e]); }
-  if constexpr (EPI == 2) {                         // r0 = 8 hi halves, r1 = 8 lo halves of channels 8o .. 8o+7
-    const h8 rh = __builtin_bit_cast(h8, r.r0), rl = __builtin_bit_cast(h8, r.r1);
+  if constexpr (EPI == 2) {                         // ring slot = {8 hi halves, 8 lo halves} of channels 8o .. 8o+7
+    const h8 rh = __builtin_bit_cast(h8, r.res[P % H2_RES_LEAD][0]), rl = __builtin_bit_cast(h8, r.res[P % H2_RES_LEAD][1]);
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = fmaf((float)rh[e] + (float)rl[e], res_mul, v[e]);
   }
@@ -163,6 +219,8 @@ __device__ __forceinline__ void h2_epi_rest(const ConvArgs& a, const EpiTile& t,
   if constexpr (P < 4 * NT) {
     h2_epi_load<NT, EPI, P>(a, t, stg, sb, wave, lane, r);
     h2_epi_compute<NT, EPI, P>(a, t, r, res_mul);
+    // (the first H2_RES_LEAD passes' residual rows are on their way or here; the others go out as soon as their slot is free)
+    if constexpr (EPI == 2 && P + H2_RES_LEAD < 4 * NT) h2_epi_res_load<NT, P + H2_RES_LEAD>(a, t, wave, lane, r);
     h2_epi_rest<NT, EPI, P + 1>(a, t, stg, sb, wave, lane, r, res_mul);
   }
 }
@@ -314,6 +372,9 @@ __device__ __forceinline__ void h2_dma_rows(const ConvArgs& a, const PipeDma& dm
 // (PW_X_*: timing-only ablation switches -- each leaves one piece of a tap's side work out, or makes it trivial, and computes
 // WRONG results; built by tools/build_variant.py into variant libraries, never into libpreworld_hip.so.  Their table, and why half
 // of it measures the power cap rather than the piece left out: profiles/r03_conv_h2_ablation.txt.)
+#ifndef PW_CONV_TAP_PROBE_STAGE
+#define PW_CONV_TAP_PROBE_STAGE 3       // the stage of block 17 whose taps PW_CONV_TAP_PROBE times (tools/probe_conv_pipe.py)
+#endif
 template <int NT, int EPI, int TAP, bool WR = false, int NW = 1>
 __device__ __forceinline__ void h2_step(const ConvArgs& a, const H2Ctx<NT>& c, const unsigned (&aaddr)[2][3][4],
                                         v4f (&ac)[2][4], v4f (&an)[2][4], v4f (&b0)[NT][4], v4f (&b1)[NT][4],
@@ -329,8 +390,9 @@ __device__ __forceinline__ void h2_step(const ConvArgs& a, const H2Ctx<NT>& c, c
   constexpr bool epi_tap = false, epi_ld = false;
 #else
   constexpr bool epi_tap = EPI > 0 && TAP >= 2 && TAP <= 4 * NT + 1;      // pass TAP-2 of the previous tile (loaded last tap)
-  constexpr bool epi_ld = EPI > 0 && TAP >= 1 && TAP <= 4 * NT;           // loads of pass TAP-1
+  constexpr bool epi_ld = EPI > 0 && TAP >= 1 && TAP <= 4 * NT;           // LDS loads of pass TAP-1
 #endif
+  constexpr bool res_ld = EPI == 2 && epi_tap && TAP - 2 + H2_RES_LEAD < 4 * NT;      // residual rows of pass TAP-2+LEAD into the slot pass TAP-2 frees
 #ifdef PW_X_BSAME
   h2_load_b<NT, WR>(c.wr, c.wsoff, c.lane_off, b2);
 #elif !defined(PW_X_NOB)
@@ -347,15 +409,16 @@ __device__ __forceinline__ void h2_step(const ConvArgs& a, const H2Ctx<NT>& c, c
   if constexpr (TAP < 26) h2_read_a_tap<TAP + 1>(c.lds3, aaddr, an);
 #endif
   if constexpr (epi_tap) h2_epi_compute<NT, EPI, TAP - 2>(a, c.epi, er, c.res_mul);
+  if constexpr (res_ld) h2_epi_res_load<NT, TAP - 2 + H2_RES_LEAD>(a, c.epi, c.wave, c.lane, er);
   if constexpr (epi_ld)
     h2_epi_load<NT, EPI, TAP - 1>(a, c.epi, c.ldsg + c.epi.bufoff + (unsigned)c.wave * (TW * 128),
                                   reinterpret_cast<const float*>(c.ldsg + H2_SB_OFF), c.wave, c.lane, er);
   h2_mfma<NT, WR, TAP, NW>(ac, b0, acc, wres);
   {
-    constexpr int n_vm = (WR ? 2 : 4) * NT + 2 * dma_n + ((epi_ld && EPI == 2) ? 2 : 0);
+    constexpr int n_vm = (WR ? 2 : 4) * NT + 2 * dma_n + (res_ld ? 2 : 0);
     constexpr int n_ds = (TAP < 26 ? 8 : 0) + (epi_ld ? 6 : 0);
-    constexpr int n_sa = 4 + 26 * dma_n + (epi_ld ? 12 : 0);
-    constexpr int n_va = 5 * dma_n + (epi_tap ? (EPI == 2 ? 100 : 76) : 0) + (epi_ld ? 36 : 0);
+    constexpr int n_sa = 4 + 26 * dma_n + (epi_ld ? 12 : 0) + (res_ld ? 20 : 0);        // res_ld: tile base + row step + descriptor
+    constexpr int n_va = 5 * dma_n + (epi_tap ? (EPI == 2 ? 100 : 76) : 0) + (epi_ld ? 36 : 0) + (res_ld ? 8 : 0);
     h2_pipeline<0, 12 * NT, n_vm, n_ds, n_sa, n_va>();
     if constexpr (epi_tap) __builtin_amdgcn_sched_group_barrier(0x040, 2, 0);
   }
@@ -578,6 +641,11 @@ __global__ void __launch_bounds__(256, 1) k_conv3d_h2(ConvArgs a, PipeArgs p) {
     long long ts0 = 0, ts1 = 0, ts2 = 0;
     if (a.probe) ts0 = __builtin_readcyclecounter();
     h2_read_a_tap<0>(c.lds3, aaddr, a0);
+    if constexpr (EPI == 2) {          // residual rows of the parked tile, second half ("Residual lead"): nothing parked = out of range
+      __builtin_amdgcn_sched_barrier(0);
+      h2_epi_res_range<NT, H2_RES_AT_PARK, H2_RES_AT_PARK + 1>(a, c.epi, wave, lane, er);
+      __builtin_amdgcn_sched_barrier(0);
+    }
 
     // next stage: next chunk of this tile, else chunk 0 of the block's next item
     PipeTile tn = t;
@@ -594,7 +662,11 @@ __global__ void __launch_bounds__(256, 1) k_conv3d_h2(ConvArgs a, PipeArgs p) {
     c.dm_pitch = (unsigned)(a.W * a.Cin) * 4u;
     c.dm_base = (unsigned)(((((tn.b * a.D + tn.d0 - 1) * a.H + tn.h0 - 1) * a.W + c.dm.wbase) * a.Cin + chn * KC) * 4);
 
-    c.tap_probe = (a.probe && blockIdx.x == 17 && stage == 3) ? a.probe + 256 * 8 * 16 * 4 : nullptr;
+    if constexpr (EPI == 2) {
+      __builtin_amdgcn_sched_barrier(0);
+      h2_epi_res_range<NT, H2_RES_AT_PARK + 1, H2_RES_LEAD>(a, c.epi, wave, lane, er);
+    }
+    c.tap_probe = (a.probe && blockIdx.x == 17 && stage == PW_CONV_TAP_PROBE_STAGE) ? a.probe + 256 * 8 * 16 * 4 : nullptr;
     h2_step<NT, EPI, 0, WR, NW>(a, c, aaddr, a0, a1, b0, b1, b2, acc, er, wres);
     if (a.probe) ts1 = __builtin_readcyclecounter();
 
@@ -614,6 +686,7 @@ __global__ void __launch_bounds__(256, 1) k_conv3d_h2(ConvArgs a, PipeArgs p) {
         h2_epi_park<NT>(acc, stg, lane);
         c.epi.b = t.b; c.epi.d0 = t.d0; c.epi.h0 = t.h0; c.epi.w0 = t.w0; c.epi.ng = t.ng; c.epi.bufoff = bufoff;
         c.epi.pending = true;
+        if constexpr (EPI == 2) h2_epi_res_range<NT, 0, H2_RES_AT_PARK>(a, c.epi, wave, lane, er);
       }
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt)
@@ -631,6 +704,7 @@ __global__ void __launch_bounds__(256, 1) k_conv3d_h2(ConvArgs a, PipeArgs p) {
   }
   // the last tile of this block has no next stage to ride on
   if constexpr (EPI > 0) {
+    if constexpr (EPI == 2) { if (c.epi.pending) h2_epi_res_range<NT, H2_RES_AT_PARK, H2_RES_LEAD>(a, c.epi, wave, lane, er); }
     if (c.epi.pending)
       h2_epi_rest<NT, EPI, 0>(a, c.epi, reinterpret_cast<const char*>(lds) + c.epi.bufoff + (unsigned)wave * (TW * 128),
                               lds + H2_SB_OFF / 4, wave, lane, er, rs.res);

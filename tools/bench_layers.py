@@ -1,7 +1,10 @@
 """Sustained timing of every conv layer shape of the C3 encoder (one line per shape).
 LOOP_S seconds per shape.
 ALGO=<0..3> picks the direct kernel (pw_conv3d_ndhwc's algo); EPI=1 adds scale/bias + in-place residual + ReLU to the Winograd runs.  ALGO=wino runs the Winograd kernel on the
-shapes it supports (k3 s1, <= 64 output columns) and skips the others.  TFLOP/s are direct-form FLOPs / time."""
+shapes it supports (k3 s1, <= 64 output columns) and skips the others.  TFLOP/s are direct-form FLOPs / time.
+Without ALGO every 3x3x3 stride-1 shape also gets two columns for the split-fp16 kernel (pw_conv3d_h2) with h2 input and output:
+"h2->h2" (scale / bias / ReLU) and "h2->h2 + residual" (the same plus an h2 residual, BasicBlock3D's tail; out of place here so that the data stay the same from call to call)
+-- their difference is what the residual epilogue costs at that shape."""
 import json
 import os
 import sys
@@ -56,5 +59,29 @@ for (D, H, W, ci, co, ks, st) in SHAPES:
     dt = (time.time() - t0) / n
     flops = 2.0 * (D // st) * (H // st) * (W // st) * ks ** 3 * ci * co
     res[key] = dict(us=round(dt * 1e6, 1), tflops=round(flops / dt * 1e-12, 1))
-    print('%-28s %8.1f us  %6.1f TFLOP/s' % (key, dt * 1e6, flops / dt * 1e-12), flush=True)
+    line = '%-28s %8.1f us  %6.1f TFLOP/s' % (key, dt * 1e6, flops / dt * 1e-12)
+    if ks == 3 and st == 1 and os.environ.get('ALGO') is None:
+        xh = ops.f32_to_h2(x)
+        wh, inv = ops.pack_conv_weight_h2(torch.randn(co, ci, 3, 3, 3, device=dev) * 0.05)
+        sc, bi = (torch.rand(co, device=dev) * 0.2 + 0.4) * inv, torch.randn(co, device=dev)
+        yh, rh = ops.f32_to_h2(torch.randn(1, D, H, W, co, device=dev)), ops.f32_to_h2(torch.randn(1, D, H, W, co, device=dev))
+        for col, kw in (('h2->h2', {}), ('h2->h2 + residual', dict(residual=rh))):
+            fn = lambda: ops.conv3d_h2(xh, wh, sc, bi, relu0=True, out0=yh, **kw)
+            for _ in range(5):
+                fn()
+            torch.cuda.synchronize()
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            n, t0 = 0, time.time()
+            ev0.record()
+            while time.time() - t0 < loop_s / 2:
+                for _ in range(20):
+                    fn()
+                torch.cuda.synchronize()
+                n += 20
+            ev1.record()
+            torch.cuda.synchronize()
+            us = ev0.elapsed_time(ev1) * 1e3 / n
+            res[key][col + ' us'] = round(us, 1)
+            line += '   %s %6.1f us' % (col, us)
+    print(line, flush=True)
 print(json.dumps(dict(env={k: v for k, v in os.environ.items() if k.startswith('PW_')}, layers=res)))

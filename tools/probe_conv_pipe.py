@@ -1,6 +1,8 @@
 """Per-stage phase timestamps of the persistent DMA-pipelined conv kernel (development aid).
 PW_CONV_PROBE=<device ptr> makes k_conv3d_k3s1_pipe write, for each wave and each of its first 16
-stages, the cycle counter at {stage start, taps done, barrier passed, epilogue done}."""
+stages, the cycle counter at {stage start, taps done, barrier passed, epilogue done}.
+A library built with -DPW_CONV_TAP_PROBE (tools/build_variant.py) also records the start of every tap of one stage of block 17:
+stage 3, or -DPW_CONV_TAP_PROBE_STAGE=<n>.  H2=1 probes k_conv3d_h2, H2=1 RES=1 its residual epilogue."""
 import os
 import sys
 
@@ -33,9 +35,17 @@ if os.environ.get('OCC', '0') == '1':         # k_occ_head_h2 (same probe layout
 elif os.environ.get('H2', '0') == '1':        # the split-fp16 kernel k_conv3d_h2 (same probe layout)
     wh, inv = ops.pack_conv_weight_h2(torch.randn(cout, cin, 3, 3, 3, device=dev) * 0.05)
     xh = ops.f32_to_h2(x)
-    for _ in range(3):
-        buf.zero_()
-        ops.conv3d_h2(xh, wh, inv)
+    if os.environ.get('RES', '0') == '1':     # BasicBlock3D's tail: h2 residual added in place, ReLU (the EPI == 2 epilogue passes)
+        yh = ops.f32_to_h2(torch.randn(1, dims[0], dims[1], dims[2], cout, device=dev))
+        for _ in range(3):
+            buf.zero_()
+            ops.conv3d_h2(xh, wh, inv, residual=yh, relu0=True, out0=yh)
+    else:
+        for _ in range(3):
+            buf.zero_()
+            ops.conv3d_h2(xh, wh, inv)
+    from preworld_amd import _lib  # noqa: E402
+    print('kernel:', _lib.lib().pw_last_kernel().decode())
 else:
     w = ops.pack_conv_weight(torch.randn(cout, cin, 3, 3, 3, device=dev) * 0.05)
     for _ in range(3):
@@ -80,7 +90,7 @@ for st in (3, 4):
     base = t[b, :, st, 0].min()
     print('block %d stage %d:' % (b, st), ' '.join('w%d[%.0f..%.0f]' % (w, t[b, w, st, 0] - base, t[b, w, st, 1] - base) for w in range(8)))
 
-print('per-tap start times (block 17, stage 3), relative to the earliest wave:')
+print('per-tap start times (block 17, the probed stage), relative to the earliest wave:')
 base = taps[:, 0].min()
 for w in range(8):
     print('w%d' % w, ' '.join('%5.0f' % (v - base) for v in taps[w]))
